@@ -10,8 +10,17 @@ Weak scaling: at N GPUs the sweep-rate axis is refined N-fold (1000 x 1000N grid
 rank owns a contiguous 1e6-point shard; the per-point yield tables (48 B/point) are
 all-gathered over RCCL at the end of every step (north_star (3)).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline fields, the
+devices and the per-rank step decomposition (`kernel_ms` / `allgather_ms`, from HIP events the
+timed steps record anyway).  `--dump-outputs DIR` also writes the yield table of the last timed
+step (what a caller of the sweep receives) to DIR/yields.npy, float64; the grid is fixed, so two
+builds run with the same arguments can be compared row for row.  Everything else described below
+(`roofline`, `evidence` / `parity_spot`, `reuse_zsums`, `truncated`, `cpu_baseline`) runs only with
+`--full`, after the timed steps, and `--no-cpu-baseline` / `--no-parity-spot` / `--no-reuse` /
+`--truncated` / `--cpu-seconds` select among those legs.
 
 `python bench.py --gpus N` with N > 1 and no launcher (no WORLD_SIZE in the environment) starts
 the N ranks itself: the parent touches no GPU, runs this same script under
@@ -280,6 +289,23 @@ def parity_spot(axes, start: int, table: torch.Tensor, n: int = 64) -> dict:
                       f"vs oracle/lzq_oracle.c (pinned to the reference's golden outputs)"}
 
 
+DUMP_MAX_ROWS = 1_000_000   # 48 MB of float64 rows (+ 8 MB of row indices when sampled): under 64 MB in all
+
+
+def dump_outputs(path: str, table: torch.Tensor) -> None:
+    """--dump-outputs: the gathered yield table of the last timed step (rows = grid points in
+    grid order, columns = _native.YIELD_FIELDS) as path/yields.npy, float64.  Beyond DUMP_MAX_ROWS
+    rows (N > 1 GPUs) a fixed sample of rows, numpy default_rng(0), sorted, with their grid
+    indices beside them in path/yields_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    n = table.shape[0]
+    if n > DUMP_MAX_ROWS:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=DUMP_MAX_ROWS, replace=False))
+        table = table[torch.as_tensor(idx, device=table.device)]
+        np.save(os.path.join(path, "yields_rows.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "yields.npy"), np.ascontiguousarray(table.cpu().numpy(), dtype=np.float64))
+
+
 class Clock:
     """Marks on the timed stream: HIP events on the GPU (elapsed on the device clock), host
     perf_counter after a synchronize otherwise (the CPU rehearsal of tests/test_bench_roofline.py)."""
@@ -372,13 +398,18 @@ def launch_ranks(argv: list, n: int) -> int:
 def main(argv=None, engine=None) -> int:
     """The bench (one JSON line on rank 0).  engine: a stand-in with Engine.sweep's signature and a
     torch `device` (tests only: the CPU rehearsal of the timing / evidence order); None = the HIP
-    engine on this rank's GPU.  Returns the exit status: non-zero when the timed table fails its
-    evidence checks (non-finite rows, a misplaced shard, parity_spot beyond the guard band)."""
+    engine on this rank's GPU.  Returns the exit status: non-zero when, with --full, the timed table
+    fails its evidence checks (non-finite rows, a misplaced shard, parity_spot beyond the guard band)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--points", type=int, default=1_000_000, help="points per GPU per step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's yield table (rank 0, after the gather) to DIR/yields.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the evidence checks (finite / placed / parity_spot), the "
+                         "roofline, the secondary reuse / truncated legs and the CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity-spot", action="store_true", help="skip the oracle check of 64 timed rows")
     ap.add_argument("--truncated", action="store_true",
@@ -393,6 +424,9 @@ def main(argv=None, engine=None) -> int:
     args = ap.parse_args(argv)
     if args.gpus < 1:
         print(f"[bench] --gpus {args.gpus}: need at least 1", file=sys.stderr)
+        return 2
+    if args.truncated and not args.full:
+        print("[bench] --truncated is a leg of --full", file=sys.stderr)
         return 2
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(argv, args.gpus)
@@ -501,19 +535,27 @@ def main(argv=None, engine=None) -> int:
     # Evidence on the TIMED table, before the secondary legs below overwrite local_tab: every row
     # of the gathered table finite, rank r's rows at [r*per, (r+1)*per), and parity_spot's oracle
     # rows (rank 0) from the dense table of the last timed step.
-    finite = bool(torch.isfinite(gathered).all())
-    placed = bool(torch.equal(gathered[start:start + per], local_tab)) if use_dist else True
-    spot = parity_spot(axes, start, local_tab) if rank == 0 and not args.no_parity_spot else None
-    ok = torch.tensor([1.0 if finite and placed else 0.0], dtype=torch.float64, device=eng.device if nccl else "cpu")
-    if use_dist:
-        dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-    evidence = {"table": "dense timed table (last timed step), checked before the secondary legs",
-                "all_finite_and_placed": bool(ok.item() == 1.0), "parity_spot_ok": None if spot is None else spot["ok"]}
+    # All of it only with --full; a plain run ends with the dump and the line.
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, gathered)
+    spot = evidence = None
+    if args.full:
+        finite = bool(torch.isfinite(gathered).all())
+        placed = bool(torch.equal(gathered[start:start + per], local_tab)) if use_dist else True
+        spot = parity_spot(axes, start, local_tab) if rank == 0 and not args.no_parity_spot else None
+        ok = torch.tensor([1.0 if finite and placed else 0.0], dtype=torch.float64,
+                          device=eng.device if nccl else "cpu")
+        if use_dist:
+            dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+        evidence = {"table": "dense timed table (last timed step), checked before the secondary legs",
+                    "all_finite_and_placed": bool(ok.item() == 1.0),
+                    "parity_spot_ok": None if spot is None else spot["ok"]}
 
     # Secondary (NOT the headline): the same step with exact-underflow truncation of the
     # z-sums (LZQ_TUNE_TRUNCATE), which skips nodes whose terms cannot change the FP64 sums;
     # its table must be bit-identical to the dense one.
-    dense_tab = local_tab.clone() if (args.truncated or args.reuse) else None
+    reuse_leg = args.full and args.reuse
+    dense_tab = local_tab.clone() if (args.truncated or reuse_leg) else None
     trunc = None
     if args.truncated:
         eng.tune_truncate(True)
@@ -535,7 +577,7 @@ def main(argv=None, engine=None) -> int:
     # Secondary (NOT the headline): the z-sums computed once per y-grid / A/V kernel and shared
     # by the points (lzq_sweep_grid_reuse); the table must be bit-identical to the dense one.
     reuse = None
-    if args.reuse:
+    if reuse_leg:
         eng.sweep(BASE, axes, start, per, out=local_tab, reuse=True)   # warm-up (table workspace)
         clock.sync()
         t1 = time.perf_counter()
@@ -551,7 +593,7 @@ def main(argv=None, engine=None) -> int:
                  "note": "z-sums shared by the points of one y-grid / A/V kernel (include/lzq.h "
                          "lzq_sweep_grid_reuse; the C2 grid has one); one step, not the headline"}
 
-    status = 0 if evidence["all_finite_and_placed"] and (spot is None or spot["ok"]) else 1
+    status = 0 if evidence is None or (evidence["all_finite_and_placed"] and (spot is None or spot["ok"])) else 1
     if rank == 0:
         rec = {
             "metric": METRIC,
@@ -576,21 +618,25 @@ def main(argv=None, engine=None) -> int:
                        "points_per_gpu": per, "global_points_per_step": total, "n_y": 8000, "nz": 1200,
                        "parallelism": f"grid-sharded x{world}, {'RCCL' if nccl else 'gloo'} "
                                       f"all-gather of 48 B/point yield tables"},
-            "roofline": roofline(per, kern_ms) if cuda else None,
             # the step decomposed per rank (means over the timed steps): the sweep kernel (HIP
             # events around it) and the all-gather of the yield table (events after it), so a
             # sub-linear SCALE curve can be attributed to compute imbalance or to the collective
             "kernel_ms": spread(every[:, 1]),
             "allgather_ms": spread(every[:, 2]) if use_dist else None,
-            "evidence": evidence,
+            "full": args.full,
         }
+        if args.dump_outputs is not None:
+            rec["dump_outputs"] = args.dump_outputs
+        if args.full:
+            rec["roofline"] = roofline(per, kern_ms) if cuda else None
+            rec["evidence"] = evidence
         if spot is not None:
             rec["parity_spot"] = spot
         if trunc is not None:
             rec["truncated"] = trunc
         if reuse is not None:
             rec["reuse_zsums"] = reuse
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # after every collective of the run (the other ranks are done), at every N (north_star:
             # the CPU path beside the throughput at 1/2/4/8 GPUs); the sample is the same grid's
             rec["cpu_baseline"] = cpu_baseline(axes, grid_total, args.cpu_seconds)

@@ -60,7 +60,7 @@ import socket
 import subprocess
 
 FAKE = os.path.join(ROOT, "tests", "bench_fake.py")
-SMALL = ["--points", "64", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+SMALL = ["--full", "--points", "64", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
 
 
 def _run(cmd, env=None):
@@ -122,7 +122,7 @@ def test_gpus_n_without_launcher_spawns_the_ranks():
     (torch.distributed.run of the same script), and the one line it lets through measured both:
     n_gpus 2, the all-gather timed on both ranks, and the CPU baseline beside it (north_star: at
     every N)."""
-    r = _run([sys.executable, FAKE, "--gpus", "2", "--points", "64", "--steps", "2", "--warmup", "1", "--no-reuse",
+    r = _run([sys.executable, FAKE, "--full", "--gpus", "2", "--points", "64", "--steps", "2", "--warmup", "1", "--no-reuse",
               "--no-parity-spot", "--dist-backend", "gloo", "--cpu-seconds", "0.5"])
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _line(r.stdout)
@@ -144,7 +144,7 @@ def test_n_rank_line_names_distinct_devices():
     """at N > 1 the line carries the process group's own world size and backend
     and one device record per rank (PCI bus id, UUID, host), and counts the distinct devices; the
     CPU baseline is still there."""
-    r = _run([sys.executable, FAKE, "--gpus", "2", "--points", "64", "--steps", "2", "--warmup", "1", "--no-reuse",
+    r = _run([sys.executable, FAKE, "--full", "--gpus", "2", "--points", "64", "--steps", "2", "--warmup", "1", "--no-reuse",
               "--no-parity-spot", "--dist-backend", "gloo", "--cpu-seconds", "0.5"])
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _line(r.stdout)
@@ -158,7 +158,7 @@ def test_n_rank_line_names_distinct_devices():
 def test_two_ranks_on_one_device_exit_nonzero():
     """Two ranks that report the same device (a stand-in claiming exclusive devices, as RCCL ranks
     are): exit 2 before any timing, no line."""
-    r = _run([sys.executable, FAKE, "--gpus", "2", "--points", "64", "--steps", "2", "--warmup", "1", "--no-reuse",
+    r = _run([sys.executable, FAKE, "--full", "--gpus", "2", "--points", "64", "--steps", "2", "--warmup", "1", "--no-reuse",
               "--no-parity-spot", "--dist-backend", "gloo", "--no-cpu-baseline"], env={"FAKE_DUP_DEVICE": "1"})
     assert r.returncode != 0
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -171,3 +171,77 @@ def test_single_rank_line_names_its_device():
     rec = _line(r.stdout)
     assert rec["world_size"] == 1 and rec["dist_backend"] is None and rec["distinct_devices"] == 1
     assert len(rec["devices"]) == 1 and rec["devices"][0]["rank"] == 0
+
+
+# ---- the plain run (no --full) and --dump-outputs ---------------------------------------------
+FULL_ONLY = ("roofline", "evidence", "parity_spot", "reuse_zsums", "truncated", "cpu_baseline")
+
+
+def _main_counting(argv, capsys):
+    """bench.main in this process on the stand-in engine, counting its sweeps."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import bench_fake
+
+    class Counting(bench_fake.FakeEngine):
+        calls = 0
+
+        def sweep(self, *a, **kw):
+            Counting.calls += 1
+            return super().sweep(*a, **kw)
+
+    eng = Counting()
+    from unittest import mock
+    env = {k: v for k, v in os.environ.items() if k not in ("MASTER_ADDR", "MASTER_PORT", "WORLD_SIZE", "RANK")}
+    with mock.patch.dict(os.environ, env, clear=True):
+        rc = bench.main(argv, engine=eng)
+    return rc, _line(capsys.readouterr().out), Counting.calls, eng
+
+
+def test_plain_run_only_warms_up_and_times_its_steps(capsys):
+    """Without --full the engine is called warmup + steps times and nothing else runs: the line has
+    the headline fields and ms_per_step, and none of the --full legs."""
+    rc, rec, calls, _ = _main_counting(["--gpus", "1", "--points", "64", "--steps", "3", "--warmup", "2"], capsys)
+    assert rc == 0 and calls == 5
+    assert rec["steps"] == 3 and rec["warmup"] == 2 and rec["full"] is False
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "kernel_ms"):
+        assert k in rec, k
+    assert rec["unit"] == "points/s" and rec["higher_is_better"] is True and rec["dtype"] == "f64"
+    assert rec["ms_per_step"] > 0 and abs(rec["value"] - 64 / (rec["ms_per_step"] / 1e3)) <= 1e-6 * rec["value"]
+    assert not [k for k in FULL_ONLY if k in rec]
+
+
+def test_truncated_needs_full():
+    r = _run([sys.executable, FAKE, "--points", "64", "--steps", "1", "--warmup", "0", "--truncated"])
+    assert r.returncode == 2 and not [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert "--full" in r.stderr
+
+
+def test_dump_outputs_is_the_last_timed_table(tmp_path, capsys):
+    """--dump-outputs writes the table the timed path returned in its last step, float64, the same
+    from run to run; with --full it is written before the secondary legs reuse the buffer (the
+    stand-in writes NaN in those)."""
+    import numpy as np
+    args = ["--points", "64", "--steps", "2", "--warmup", "1"]
+    rc, rec, calls, eng = _main_counting(args + ["--dump-outputs", str(tmp_path / "a")], capsys)
+    assert rc == 0 and rec["dump_outputs"] == str(tmp_path / "a")
+    a = np.load(tmp_path / "a" / "yields.npy")
+    assert sorted(os.listdir(tmp_path / "a")) == ["yields.npy"]
+    assert a.dtype == np.float64 and a.shape == (64, 6) and np.isfinite(a).all()
+    assert np.array_equal(a, eng._cache[(0, 64)].numpy())
+    r = _run([sys.executable, FAKE, "--full", "--no-cpu-baseline", *args, "--dump-outputs", str(tmp_path / "b")])
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert np.array_equal(a, np.load(tmp_path / "b" / "yields.npy"))
+
+
+def test_dump_outputs_samples_a_large_table(tmp_path, monkeypatch):
+    """Beyond DUMP_MAX_ROWS rows the dump is a fixed sorted sample with its row indices."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_MAX_ROWS", 10)
+    t = torch.arange(600, dtype=torch.float64).reshape(100, 6)
+    bench.dump_outputs(str(tmp_path / "a"), t)
+    bench.dump_outputs(str(tmp_path / "b"), t)
+    rows, tab = np.load(tmp_path / "a" / "yields_rows.npy"), np.load(tmp_path / "a" / "yields.npy")
+    assert rows.dtype == np.float64 and rows.shape == (10,) and (np.diff(rows) > 0).all()
+    assert tab.dtype == np.float64 and np.array_equal(tab, t.numpy()[rows.astype(int)])
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "yields_rows.npy"))

@@ -64,7 +64,7 @@ def test_sweep_two_ranks_bit_identical_to_one(tmp_path):
 def test_bench_multi_rank_gloo(world):
     """bench.py's N > 1 path (rank shards of the W-fold refined grid, the per-step gather,
     barrier + max-over-ranks timing) with W ranks sharing the one GPU."""
-    out = run(torchrun(world) + ["bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "1", "--points",
+    out = run(torchrun(world) + ["bench.py", "--full", "--gpus", str(world), "--steps", "1", "--warmup", "1", "--points",
                                  "20000", "--dist-backend", "gloo"], 300)
     recs = [json.loads(l) for l in out.splitlines() if l.startswith("{")]
     assert len(recs) == 1
@@ -78,7 +78,7 @@ def test_bench_multi_rank_gloo(world):
 def test_bench_single_rank_line():
     """bench.py at N = 1 (small): one JSON line with the contract's fields, a roofline fraction
     in (0, 1] from executed FP64 FLOP, and the CPU baseline on every CPU of this job."""
-    out = run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--points", "50000",
+    out = run([sys.executable, "bench.py", "--full", "--steps", "1", "--warmup", "1", "--points", "50000",
                "--cpu-seconds", "1"], 300)
     recs = [json.loads(l) for l in out.splitlines() if l.startswith("{")]
     assert len(recs) == 1
@@ -112,8 +112,8 @@ def test_rccl_one_rank_bench_line():
     """bench.py under a 1-rank torchrun takes the RCCL branch (process group, per-step
     all_gather_into_tensor, barrier, max-over-ranks all_reduce on the device) and still emits
     one valid line."""
-    out = run(torchrun(1) + ["bench.py", "--gpus", "1", "--steps", "1", "--warmup", "1", "--points", "20000",
-                             "--no-cpu-baseline"], 300)
+    out = run(torchrun(1) + ["bench.py", "--full", "--gpus", "1", "--steps", "1", "--warmup", "1", "--points",
+                             "20000", "--no-cpu-baseline"], 300)
     recs = [json.loads(l) for l in out.splitlines() if l.startswith("{")]
     assert len(recs) == 1
     r = recs[0]
@@ -130,3 +130,28 @@ def test_sweep_two_ranks_reuse_equals_dense(tmp_path):
     run(torchrun(2) + ["-m", PKG_NAME + ".sweep", *args, "--out", str(two), "--dist-backend", "gloo",
                        "--reuse-zsums"], 300)
     assert np.array_equal(np.load(one / "table.npy"), np.load(two / "table.npy"))
+
+
+def test_bench_plain_line_and_dump(tmp_path):
+    """A plain bench.py run (no --full) on the real engine: the headline fields and ms_per_step
+    without the --full legs, and --dump-outputs holds the timed table: 8 of its rows against the C
+    oracle within parity_spot's guard band."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import oracle as O
+    n = 20000
+    out = run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--points", str(n),
+               "--dump-outputs", str(tmp_path)], 300)
+    recs = [json.loads(l) for l in out.splitlines() if l.startswith("{")]
+    assert len(recs) == 1
+    r = recs[0]
+    assert r["steps"] == 2 and r["full"] is False and r["dtype"] == "f64" and r["unit"] == "points/s"
+    assert r["value"] > 0 and abs(r["value"] - n / (r["ms_per_step"] / 1e3)) <= 1e-6 * r["value"]
+    assert not [k for k in ("roofline", "evidence", "parity_spot", "reuse_zsums", "truncated", "cpu_baseline") if k in r]
+    tab = np.load(tmp_path / "yields.npy")
+    assert tab.dtype == np.float64 and tab.shape == (n, 6) and np.isfinite(tab).all()
+    idx = np.linspace(0, n - 1, 8).astype(int)
+    ref = O.points_batch([bench.grid_config(bench.grid_axes(1), int(i), O) for i in idx])
+    err = np.abs(tab[idx] - ref) / np.where(ref != 0.0, np.abs(ref), 1.0)
+    print("bench dump vs oracle, worst rel", err.max())
+    assert err.max() < 1e-11

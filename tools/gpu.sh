@@ -1,7 +1,7 @@
 # The one GPU-box launcher (run through gpurun from the repo root):
 #
 #   gpurun -- bash tools/gpu.sh tests [pytest args ...]   the -m gpu suite (or a selection), one process
-#   gpurun -- bash tools/gpu.sh final                     full -m gpu suite, smoke(), the default bench line
+#   bash tools/gpu.sh final                               full -m gpu suite, smoke(), the bench line with --full
 #   gpurun -- bash tools/gpu.sh profile ROUND             rocprofv3 --kernel-trace --stats of the driver's
 #                                                         bench command, the PMC passes of the headline
 #                                                         kernel, profiles/ROUND summary, then the bench
@@ -9,7 +9,7 @@
 #   gpurun -- bash tools/gpu.sh prop-pmc [N]              bounce-profile propagation PMC + kernel trace
 #   gpurun -- bash tools/gpu.sh lzprop-pmc                LZ propagator PMC + kernel trace (C5 slice)
 #   gpurun -- [REUSE=1] bash tools/gpu.sh sweeps [SPECS]  full grids through the sweep CLI (+ reuse bitwise)
-#   gpurun -- bash tools/gpu.sh bench [bench args ...]    one bench line
+#   bash tools/gpu.sh bench [bench args ...]              one bench line (plain; pass --full for every leg)
 #   gpurun -- bash tools/gpu.sh py SCRIPT [args ...]      any tools/ script (ablations, ODE / profile benches)
 #
 # Every GPU step runs under its own timeout and the steps are chained: a failure, abort or
@@ -37,17 +37,17 @@ case "$cmd" in
     timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 \
       || { tail -20 "$OUT/smoke.log"; exit 2; }
     tail -1 "$OUT/smoke.log"
-    timeout -k 10 400 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 3; }
+    timeout -k 10 400 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 3; }
     cut -c1-600 "$OUT/bench.json"
     ;;
   profile)
     ROUND=${1:?profile ROUND}
     rm -rf "$OUT"; mkdir -p "$OUT"
     timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
-      python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_traced.json" 2> "$OUT/bench_traced.err" \
+      python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_traced.json" 2> "$OUT/bench_traced.err" \
       || { tail -5 "$OUT/bench_traced.err"; exit 2; }
     cut -c1-300 "$OUT/bench_traced.json"
-    P="--points 200000 --steps 1 --warmup 0 --no-cpu-baseline --no-reuse --no-parity-spot"
+    P="--points 200000 --steps 1 --warmup 0"   # a plain run: the one kernel launch and nothing else
     pmc() { tag=$1; shift; timeout -s KILL 120 rocprofv3 --pmc "$@" --output-format csv -d "$OUT/pmc_$tag" -o run -- \
       python3 bench.py $P > "$OUT/pmc_$tag.json" 2> "$OUT/pmc_$tag.err" || { echo "pmc $tag failed"; return 1; }; }
     pmc fetch FETCH_SIZE && pmc write WRITE_SIZE && \
@@ -57,7 +57,7 @@ case "$cmd" in
     # the summary in the box's copy, so the plain bench below reports this build's roofline (the
     # host re-runs tools/summarize_profile.py on the merged gpurun_out to commit profiles/ROUND)
     python3 tools/summarize_profile.py "$OUT" "$ROUND" > "$OUT/summary.log" 2>&1 || { tail "$OUT/summary.log"; exit 5; }
-    timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.err" \
+    timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.err" \
       || { tail -20 "$OUT/bench_plain.err"; exit 3; }
     cut -c1-600 "$OUT/bench_plain.json"
     ;;
