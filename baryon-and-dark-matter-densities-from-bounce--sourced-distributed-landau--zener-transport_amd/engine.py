@@ -259,6 +259,71 @@ class Engine:
         self._keepalive = dev_vals  # axis buffers must outlive the async launch
         return out
 
+    # -- sweep fits (lzq_fit_*; fit.py holds the spec and the numpy implementation) ------------
+    def fit_state(self, fit, maps, select: bool = True) -> "FitState":
+        """An empty device-resident fit state for `fit` (fit.FitSpec) and its resolved maps
+        (fit.FitSpec.resolve); select=False leaves out the selection list (a merge target)."""
+        st = FitState(fit, maps)
+        nbytes = self.lib.lzq_fit_state_bytes(st.c_maps, len(st.maps))
+        if nbytes < 0:
+            self._check(int(nbytes))
+        st.words = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)
+        if select and fit.select is not None:
+            st.sel = torch.empty(max(1, fit.select[1]), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.lzq_fit_reset(st.c_maps, len(st.maps), _vp(st.words), self._stream()))
+        return st
+
+    def _fit_rows(self, yields: torch.Tensor) -> torch.Tensor:
+        if yields.dtype != torch.float64 or yields.dim() != 2 or yields.shape[1] != 6:
+            raise ValueError("fit: records are an (n, 6) float64 tensor in YIELD_FIELDS order")
+        return yields.to(self.device).contiguous()
+
+    def fit_update(self, state: "FitState", yields: torch.Tensor, start: int) -> None:
+        """Fold the records of flat grid indices [start, start + n) into `state`, asynchronously on
+        the current stream."""
+        y = self._fit_rows(yields)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.lzq_fit_update(state.c_terms, len(state.fit.terms), state.c_levels,
+                                                len(state.fit.levels), state.c_maps, len(state.maps), _vp(y),
+                                                int(start), y.shape[0], _vp(state.words), self._stream()))
+
+    def fit_select(self, state: "FitState", yields: torch.Tensor, start: int) -> None:
+        """Append the flat indices of the rows within fit.select's level to the state's list (kept
+        ascending by feeding chunks in ascending order); no host synchronisation."""
+        if state.fit.select is None or state.sel is None:
+            raise ValueError("fit_select: the fit has no selection")
+        y = self._fit_rows(yields)
+        level, cap = state.fit.select
+        with torch.cuda.device(self.device):
+            self._check(self.lib.lzq_fit_select(state.c_terms, len(state.fit.terms), level, _vp(y), int(start),
+                                                y.shape[0], _vp(state.words), _vp(state.sel), int(cap),
+                                                self._stream()))
+
+    def fit_merge(self, state: "FitState", words: torch.Tensor) -> None:
+        """state <- state merged with another state of the same layout (its words, from any device)."""
+        w = words.to(device=self.device, dtype=torch.int64).contiguous()
+        if w.numel() != state.words.numel():
+            raise ValueError("fit_merge: states of different layouts")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.lzq_fit_merge(state.c_maps, len(state.maps), _vp(state.words), _vp(w),
+                                               self._stream()))
+        w.record_stream(torch.cuda.current_stream(self.device))
+
+    def fit_result(self, state: "FitState", selected: Optional[torch.Tensor] = None) -> dict:
+        """The fit as host values (fit.HostFit.result's dictionary): the one device-to-host read of
+        the state, and of the kept part of the selection list (or `selected`, a list assembled
+        elsewhere)."""
+        from . import fit as _fit
+        words = state.words.cpu().numpy()
+        sel = None
+        if state.fit.select is not None:
+            if selected is not None:
+                sel = selected.cpu().numpy()
+            elif state.sel is not None:
+                sel = state.sel[:min(int(words[_fit.W_SEL_TOTAL]), state.fit.select[1])].cpu().numpy()
+        return _fit.HostFit.from_words(state.fit, state.maps, words, sel).result()
+
     # -- ODE fallback (fpy:200-219, 270-286, 385-417) ---------------------------------------
     def ode_params_to_device(self, recs: np.ndarray) -> torch.Tensor:
         """lzq_ode_params records (numpy ODE_DTYPE array) -> device byte tensor (Engine.ode's
@@ -680,6 +745,26 @@ def ode_step_counts_device(d_pts: torch.Tensor, n: int) -> torch.Tensor:
     dx = (x1 - x0).abs()
     ms = torch.minimum(torch.minimum(dx / 20000.0, x_p / 1000.0), torch.full_like(dx, 5e-4))
     return torch.where(ms > 0.0, torch.ceil(dx / ms), torch.full_like(dx, float("nan")))
+
+
+class FitState:
+    """A fit's device-resident state (Engine.fit_state): `words` (int64, include/lzq.h "fit state"),
+    `sel` (the selection list, int64[cap], or None) and the host structs of the C ABI."""
+
+    def __init__(self, fit, maps):
+        self.fit, self.maps = fit, list(maps)
+        self.words: Optional[torch.Tensor] = None
+        self.sel: Optional[torch.Tensor] = None
+        self.c_terms = (_native.LzqFitTerm * len(fit.terms))()
+        for k, t in enumerate(fit.terms):
+            self.c_terms[k].field = YIELD_FIELDS.index(t.field)
+            self.c_terms[k].target, self.c_terms[k].sigma = t.target, t.sigma
+        self.c_levels = (ctypes.c_double * max(1, len(fit.levels)))(*fit.levels)
+        self.c_maps = (_native.LzqFitMap * max(1, len(self.maps)))()
+        for k, m in enumerate(self.maps):
+            self.c_maps[k].n_axes = len(m.axes)
+            for a in range(len(m.axes)):
+                self.c_maps[k].stride[a], self.c_maps[k].len[a] = m.stride[a], m.len[a]
 
 
 class ProfileShapes:

@@ -17,6 +17,12 @@ existing chunks of the SAME definition instead of recomputing them, so a killed 
 run restarts where it stopped, and a directory written by another sweep is never mixed in
 (manifest.json records the definition; a mismatch refuses --resume).
 
+Fits (--fit FILE | paper; fit.py): every chunk, computed or resumed, is also folded on its own
+stream into a device-resident fit state (chi2 to targets: counts within levels, best point, profile
+maps, selection; lzq_fit_*), the ranks' fixed-size states are all-gathered and merged in rank order,
+and rank 0 writes fit.json, fit_maps.npz and selected.npy.  --no-table keeps only that: chunks pass
+through two chunk-sized buffers, with no shard, no all-gather and no table.npy.
+
     python -m <package>.sweep --spec C2 --out sweep_c2          # 1 GPU
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m <package>.sweep --spec C4 --out c4
 """
@@ -361,9 +367,14 @@ def _save_shard(path: str, arr: np.ndarray) -> None:
 
 def run_local(compute: ComputeFn, start: int, end: int, make_out: Callable[[int], "object"], chunk: int,
               out_dir: Optional[str] = None, resume: bool = False, sync: Callable[[], None] = lambda: None,
-              log: Callable[[str], None] = lambda s: None, key: str = ""):
+              log: Callable[[str], None] = lambda s: None, key: str = "", fit=None, keep_table: bool = True):
     """Evaluate [start, end) in chunks into one (end-start, 6) tensor, with optional
     per-chunk checkpoint files (named by `key`, see spec_key).
+
+    fit: an accumulator (fit.make_accumulator) that every chunk's rows, computed or resumed from a
+    checkpoint, are folded into on the chunk's own stream.  keep_table=False (only with a fit):
+    chunk outputs go through a ring of two chunk-sized buffers instead of an (end-start, 6) shard,
+    no checkpoint is written, and None is returned: the fit is all that is kept.
 
     On the GPU the checkpoint of chunk i is copied out on a side stream (device -> pinned host
     memory, ordered after chunk i's kernels by an event) and written by a worker thread while
@@ -372,7 +383,16 @@ def run_local(compute: ComputeFn, start: int, end: int, make_out: Callable[[int]
     (a slow disk throttles the sweep rather than pinning the whole shard).  On CPU tensors
     (tests) it is written inline."""
     import torch
-    local = make_out(end - start)
+    if not keep_table:
+        if fit is None:
+            raise ValueError("keep_table=False needs a fit")
+        if resume:
+            raise ValueError("keep_table=False cannot resume: fit-only checkpoints are not written")
+        out_dir = None
+        n_ring = max(1, min(chunk, end - start))
+        local = make_out(2 * n_ring)
+    else:
+        local = make_out(end - start)
     on_gpu = bool(getattr(local, "is_cuda", False)) and out_dir is not None
     pending = []    # (future, pinned buffer) of the writes in flight, oldest first
     ring = []       # pinned host buffers free for reuse
@@ -390,7 +410,11 @@ def run_local(compute: ComputeFn, start: int, end: int, make_out: Callable[[int]
     try:
         for c0 in range(start, end, chunk):
             n = min(chunk, end - c0)
-            view = local[c0 - start:c0 - start + n]
+            if keep_table:
+                view = local[c0 - start:c0 - start + n]
+            else:
+                slot = ((c0 - start) // chunk) % 2
+                view = local[slot * n_ring:slot * n_ring + n]
             path = _shard_file(out_dir, c0, n, key) if out_dir else None
             if path and resume and os.path.exists(path):
                 arr = np.load(path, allow_pickle=False)
@@ -403,9 +427,13 @@ def run_local(compute: ComputeFn, start: int, end: int, make_out: Callable[[int]
                     if not os.path.exists(st):
                         raise RuntimeError(f"checkpoint {path} has no ODE status record {st}")
                     counts += np.load(st, allow_pickle=False)
+                if fit is not None:
+                    fit.update(view, c0)
                 log(f"resumed {path}")
                 continue
             compute(c0, n, view)
+            if fit is not None:
+                fit.update(view, c0)
             log(f"chunk [{c0}, {c0 + n}) launched")
             if not path:
                 continue
@@ -446,7 +474,7 @@ def run_local(compute: ComputeFn, start: int, end: int, make_out: Callable[[int]
     finally:
         if on_gpu:
             pool.shutdown(wait=True)
-    return local
+    return local if keep_table else None
 
 
 def launched_distributed(world: int) -> bool:
@@ -542,9 +570,15 @@ def ode_status_summary(counts, group=None, device=None) -> Optional[dict]:
 
 
 def run_sweep(spec: SweepSpec, engine=None, rank: int = 0, world: int = 1, chunk: int = 1 << 20,
-              out_dir: Optional[str] = None, resume: bool = False, group=None, log=print, reuse: bool = False):
+              out_dir: Optional[str] = None, resume: bool = False, group=None, log=print, reuse: bool = False,
+              fit=None, keep_table: bool = True):
     """Evaluate `spec` on this rank's shard, all-gather, return the full table (torch, on
-    the engine's device)."""
+    the engine's device).
+
+    fit: a fit.FitSpec; every chunk is folded into a device-resident fit state on the sweep's
+    stream, the ranks' states are combined, and (table, fit result) is returned -- the result as
+    fit.HostFit.result gives it, the same on every rank and for every world size.
+    keep_table=False (only with a fit): no shard, no all-gather; (None, fit result)."""
     import torch
     if engine is None:
         from .engine import default_engine
@@ -553,11 +587,21 @@ def run_sweep(spec: SweepSpec, engine=None, rank: int = 0, world: int = 1, chunk
     key = prepare_out_dir(out_dir, spec, resume, rank) if out_dir else ""
 
     compute = make_compute(spec, engine, reuse=reuse)
+    acc = None
+    if fit is not None:
+        from . import fit as _fit
+        acc = _fit.make_accumulator(fit, fit.resolve(spec), engine)
+    elif not keep_table:
+        raise ValueError("keep_table=False needs a fit")
     local = run_local(compute, start, end,
                       lambda n: torch.empty((n, 6), dtype=torch.float64, device=engine.device), chunk,
-                      out_dir, resume, sync=torch.cuda.synchronize, log=log, key=key)
+                      out_dir, resume, sync=torch.cuda.synchronize, log=log, key=key, fit=acc,
+                      keep_table=keep_table)
     run_sweep.ode_status = ode_status_summary(getattr(compute, "ode_status", None), group, engine.device)
-    return gather_table(local, spec.total, rank, world, group)
+    table = gather_table(local, spec.total, rank, world, group) if keep_table else None
+    if acc is None:
+        return table
+    return table, _fit.combine(acc, world, group)
 
 
 def coherent_P(spec: SweepSpec, s: int, n: int, engine):
@@ -681,7 +725,19 @@ def main(argv=None):
                     help=f"cap on one ODE point's Radau steps (default {ODE_MAX_STEPS}; 0 = no cap)")
     ap.add_argument("--dist-backend", default="nccl",
                     help="nccl (= RCCL over xGMI, default) | gloo (rehearsal: several ranks on one GPU)")
+    ap.add_argument("--fit", default=None, metavar="FILE|paper",
+                    help="fit the yields to targets on the device, chunk by chunk: a fit-spec JSON (terms, levels, "
+                         "maps, select; see fit.py), or `paper`: Y_B = 8.72e-11 and DM_over_B = 5.357, each with "
+                         "sigma at 1%% of its target (nominal tolerances, not measurement errors).  Writes fit.json, "
+                         "fit_maps.npz, selected.npy and a \"fit\" block in summary.json")
+    ap.add_argument("--no-table", action="store_true",
+                    help="with --fit: keep only the fit -- chunks pass through two chunk-sized buffers, there is "
+                         "no all-gather, no table.npy and no checkpoint (a grid larger than HBM or the disk)")
     args = ap.parse_args(argv)
+    if args.no_table and args.fit is None:
+        ap.error("--no-table needs --fit (nothing else would be kept)")
+    if args.no_table and args.resume:
+        ap.error("--no-table --resume: a fit-only run writes no checkpoints to resume from")
 
     specs = builtin_specs()
     if args.spec in specs:
@@ -694,6 +750,11 @@ def main(argv=None):
                                             spec.z_max if args.z_max is None else args.z_max)
     if args.ode_max_steps is not None:
         spec.ode_max_steps = None if args.ode_max_steps == 0 else args.ode_max_steps
+    fitspec = fit_maps = None
+    if args.fit is not None:
+        from . import fit as _fit
+        fitspec = _fit.load(args.fit)
+        fit_maps = fitspec.resolve(spec)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -714,17 +775,24 @@ def main(argv=None):
     key = prepare_out_dir(args.out, spec, args.resume, rank) if args.out else ""
 
     compute = make_compute(spec, eng, reuse=args.reuse_zsums)
-    local = run_local(compute, start, end,
-                      lambda n: torch.empty((n, 6), dtype=torch.float64, device=eng.device), args.chunk,
+    make_out = lambda n: torch.empty((n, 6), dtype=torch.float64, device=eng.device)
+    acc = _fit.make_accumulator(fitspec, fit_maps, eng) if fitspec is not None else None
+    local = run_local(compute, start, end, make_out, args.chunk,
                       args.out, args.resume, sync=torch.cuda.synchronize,
-                      log=(print if rank == 0 else (lambda s: None)), key=key)
+                      log=(print if rank == 0 else (lambda s: None)), key=key, fit=acc,
+                      keep_table=not args.no_table)
     ode_status = ode_status_summary(getattr(compute, "ode_status", None), None, eng.device)
-    table = gather_table(local, spec_total, rank, world)
+    table = None if args.no_table else gather_table(local, spec_total, rank, world)
+    fit_result = _fit.combine(acc, world) if acc is not None else None
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     if rank == 0:
-        tab = table.cpu().numpy()
-        summ = summarize(tab, spec, elapsed)
+        if table is not None:
+            tab = table.cpu().numpy()
+            summ = summarize(tab, spec, elapsed)
+        else:   # fit only: the column extrema the fit kept stand in for summarize's statistics
+            summ = {"spec": spec.name, "n_points": int(spec_total), "fields": list(YIELD_FIELDS),
+                    "final": fit_result["columns"], "elapsed_s": elapsed}
         summ["points_per_s"] = spec_total / elapsed
         summ["n_gpus"] = world
         if ode_status is not None:
@@ -735,8 +803,16 @@ def main(argv=None):
                     "per_point" if t["per_point_chunks"] == t["chunks"] else "mixed"))
         if args.reuse_zsums:
             summ["reuse_zsums"] = eng.last_reuse
+        if fit_result is not None:
+            best = fit_result["best"]["index"]
+            fit_rep = _fit.report(fitspec, fit_result, spec, spec_total,
+                                  _fit.best_point_yields(compute, best, make_out, eng))
+            summ["fit"] = fit_rep
+            if args.out:
+                _fit.write_files(args.out, fit_rep, fit_result)
         if args.out:
-            np.save(os.path.join(args.out, "table.npy"), tab, allow_pickle=False)
+            if table is not None:
+                np.save(os.path.join(args.out, "table.npy"), tab, allow_pickle=False)
             with open(os.path.join(args.out, "summary.json"), "w") as f:
                 json.dump({**summ, "spec_def": spec.to_json()}, f, indent=2)
         print(json.dumps({k: summ[k] for k in ("spec", "n_points", "points_per_s", "n_gpus", "elapsed_s")}))

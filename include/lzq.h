@@ -493,6 +493,76 @@ int lzq_lz_propagate_profile(const double* d_knots, const double* d_coef, int32_
                              const lzq_profile_point* d_points, int64_t n, double steps_per_radian,
                              int32_t min_steps, double* d_P, void* stream);
 
+/* ---- sweep fits (no reference counterpart: a sweep's records reduced where they are) ------ */
+/* A fit folds lzq_yield records into a small device-resident state, chunk by chunk, on the
+ * caller's stream.  chi2 of a row: for each term in order d = (x - target) /
+ * sigma (IEEE division), q = d * d; chi2 = q0, then chi2 + q1, ... left to right, each operation
+ * rounded on its own (numpy's float64 expression gives the same bits).  A row is VALID iff its
+ * chi2 is finite; every other row counts in n_invalid and takes part in nothing else but the
+ * column statistics.  Everything kept is independent of the order rows arrive in (integer counts
+ * and integer atomic minima only), so the state is the same bit for bit however the rows are
+ * split into chunks, shards or ranks.
+ *
+ * The state is an array of 64-bit words:
+ *   [0] n_valid   [1] n_invalid   [2..5] n_within[l]: valid rows with chi2 <= levels[l]
+ *   [6] smallest chi2 (a double's bits; +inf with no valid row)   [7] the lowest flat grid index
+ *       attaining it (int64; -1 with no valid row)
+ *   [8..13] / [14..19] per lzq_yield column the min / max over its finite values, as the
+ *       order-preserving key k(x) = bits(x) ^ (x < 0 ? ~0 : 1 << 63) (min ~0 / max 0: no finite value)
+ *   [20..25] per column the count of non-finite values
+ *   [26] rows selected so far by lzq_fit_select   [27..31] reserved (0)
+ *   then per map, in order: chi2_min[cells] (doubles; +inf: empty cell), argmin[cells] (int64; -1).
+ * A map projects onto one or two grid axes: the cell of flat index i is i_a = (i / stride[a]) %
+ * len[a] (the C-order decode of lzq_sweep_grid: stride = the product of the later axes' lengths),
+ * and (i_0, i_1) -> i_0 * len[1] + i_1 for two axes, in the order the map names them. */
+#define LZQ_FIT_MAX_TERMS 4
+#define LZQ_FIT_MAX_LEVELS 4
+#define LZQ_FIT_MAX_MAPS 4
+#define LZQ_FIT_MAX_CELLS (1 << 24) /* per map */
+#define LZQ_FIT_HEADER_WORDS 32
+#define LZQ_FIT_MAX_INDEX ((int64_t)1 << 62) /* start + count and every stride stay at or below this */
+typedef struct lzq_fit_term {
+  int32_t field;    /* 0..5: the doubles of lzq_yield in declaration order */
+  int32_t reserved; /* 0 */
+  double target;    /* finite */
+  double sigma;     /* finite, > 0 */
+} lzq_fit_term;     /* 24 bytes */
+typedef struct lzq_fit_map {
+  int32_t n_axes;    /* 1 or 2 */
+  int32_t reserved;  /* 0 */
+  int64_t stride[2]; /* 1 .. LZQ_FIT_MAX_INDEX */
+  int64_t len[2];    /* >= 1; len[0] * len[1] <= LZQ_FIT_MAX_CELLS */
+} lzq_fit_map;       /* 40 bytes */
+
+/* Terms, levels and maps are host arrays.  LZQ_EINVAL (with a message) for more than
+ * LZQ_FIT_MAX_TERMS / _LEVELS / _MAPS entries (or no term), an unknown field, sigma <= 0 or a
+ * non-finite sigma or target, levels that are not ascending, and a map of more than
+ * LZQ_FIT_MAX_CELLS cells. */
+/* Bytes of the state for these maps (LZQ_FIT_HEADER_WORDS + 2 cells per map, 8 B each); negative:
+ * an error code. */
+int64_t lzq_fit_state_bytes(const lzq_fit_map* maps, int32_t n_maps);
+/* The empty state (no row seen). */
+int lzq_fit_reset(const lzq_fit_map* maps, int32_t n_maps, void* d_state, void* stream);
+/* Fold records d_yields[count] of flat grid indices [start, start + count) into the state: two
+ * streaming passes (minima, then the lowest index attaining each), maps of up to 4096 cells in all
+ * block-private in LDS, larger ones straight to global memory; the result does not depend on the
+ * path.  Asynchronous on `stream`; calls on one stream (or otherwise ordered) may come in any order
+ * of start. */
+int lzq_fit_update(const lzq_fit_term* terms, int32_t n_terms, const double* levels, int32_t n_levels,
+                   const lzq_fit_map* maps, int32_t n_maps, const lzq_yield* d_yields, int64_t start, int64_t count,
+                   void* d_state, void* stream);
+/* Append the flat indices of the valid rows with chi2 <= level, ascending, to d_selected at the
+ * state's running offset (word 26, which advances by the exact number selected); entries at or
+ * beyond cap are dropped.  Count, scan, scatter on `stream` with no host synchronisation (scratch:
+ * 8 B per 2048 rows, stream-ordered); chunks fed in ascending order of start on one stream leave
+ * the list ascending. */
+int lzq_fit_select(const lzq_fit_term* terms, int32_t n_terms, double level, const lzq_yield* d_yields, int64_t start,
+                   int64_t count, void* d_state, int64_t* d_selected, int64_t cap, void* stream);
+/* d_dst <- d_dst merged with d_src (two states of these maps over disjoint rows): counts add,
+ * extrema by value, a cell takes the smaller chi2 and on a tie the lower index.  The cross-rank
+ * combine of a sharded sweep. */
+int lzq_fit_merge(const lzq_fit_map* maps, int32_t n_maps, void* d_dst, const void* d_src, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
