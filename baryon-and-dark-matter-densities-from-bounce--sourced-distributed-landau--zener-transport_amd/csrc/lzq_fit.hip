@@ -29,13 +29,11 @@
 #include <string.h>
 
 #include "../../include/lzq.h"
+#include "lzq_fit_common.h"
 #include "lzq_internal.h"
 
 namespace lzq {
 
-constexpr int kFitBlock = 256;
-constexpr int kFitWaves = kFitBlock / 64;
-constexpr int kFitGrid = 512;          // blocks of the two update passes (grid-stride beyond)
 constexpr int kFitLdsCells = 4096;     // block-private map cells in LDS (32 KB: four blocks a CU)
 constexpr int kFitSelIter = 8;         // rows per thread of one selection tile
 constexpr uint64_t kInfBits = 0x7FF0000000000000ull;
@@ -44,144 +42,14 @@ constexpr uint64_t kNone = ~0ull;
 enum { W_NVALID = 0, W_NINVALID = 1, W_WITHIN = 2, W_BEST_CHI2 = 6, W_BEST_IDX = 7, W_COLMIN = 8, W_COLMAX = 14,
        W_COLBAD = 20, W_SEL_TOTAL = 26, W_HEADER = LZQ_FIT_HEADER_WORDS };
 
-struct FitMapDev {
-  int64_t stride0, len0, stride1, len1;
-  int64_t off;       // word offset of the map's chi2 cells in the state (indices follow at off + cells)
-  int32_t cells;
-  int32_t lds_off;   // first cell in the block-private LDS image, or -1: straight to global memory
-};
-
-struct FitParams {
-  int32_t n_terms, n_levels, n_maps, lds_cells;
-  int32_t field[LZQ_FIT_MAX_TERMS];
-  double target[LZQ_FIT_MAX_TERMS], sigma[LZQ_FIT_MAX_TERMS], level[LZQ_FIT_MAX_LEVELS];
-  FitMapDev map[LZQ_FIT_MAX_MAPS];
-};
-
 // order-preserving key of a double that is not NaN: a < b  <=>  key(a) < key(b) (unsigned)
 __device__ __forceinline__ uint64_t fit_key(double x) {
   const uint64_t b = (uint64_t)__double_as_longlong(x);
   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
-template <bool A16>
-__device__ __forceinline__ void fit_load_row(const lzq_yield* rows, int64_t r, double x[6]) {
-  if (A16) {   // 48-B records on a 16-B aligned base: three 16-B loads
-    const double2* q = reinterpret_cast<const double2*>(rows + r);
-    const double2 a = q[0], b = q[1], c = q[2];
-    x[0] = a.x; x[1] = a.y; x[2] = b.x; x[3] = b.y; x[4] = c.x; x[5] = c.y;
-  } else {
-    const double* q = reinterpret_cast<const double*>(rows + r);
-#pragma unroll
-    for (int j = 0; j < 6; ++j) x[j] = q[j];
-  }
-}
-
-__device__ __forceinline__ double fit_pick(const double x[6], int f) {
-  return f == 0 ? x[0] : f == 1 ? x[1] : f == 2 ? x[2] : f == 3 ? x[3] : f == 4 ? x[4] : x[5];
-}
-
-__device__ __forceinline__ double fit_chi2(const FitParams& P, const double x[6]) {
-  double c = 0.0;
-  for (int t = 0; t < P.n_terms; ++t) {
-    const double d = (fit_pick(x, P.field[t]) - P.target[t]) / P.sigma[t];
-    const double q = d * d;
-    c = t == 0 ? q : c + q;
-  }
-  return c;
-}
-
-// The cells of one thread's rows.  A thread visits flat indices flat0, flat0 + step, ...: the 64-bit
-// divisions of the decode i_a = (flat / stride_a) % len_a are done once, for flat0 and for the
-// step, and every later row costs an add, a compare and a conditional subtract per axis (the
-// divisions were most of the update's time when every row paid for them).  A 1-D map walks a
-// second axis of stride 1 and length 1, whose index stays 0.
-struct CellWalk {
-  int64_t r[LZQ_FIT_MAX_MAPS][2];     // flat % stride
-  int64_t sr[LZQ_FIT_MAX_MAPS][2];    // step % stride
-  int32_t i[LZQ_FIT_MAX_MAPS][2];     // (flat / stride) % len
-  int32_t si[LZQ_FIT_MAX_MAPS][2];    // (step / stride) % len
-
-  __device__ __forceinline__ void init(const FitParams& P, int64_t flat0, int64_t step) {
-#pragma unroll
-    for (int m = 0; m < LZQ_FIT_MAX_MAPS; ++m) {
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        r[m][a] = sr[m][a] = 0, i[m][a] = si[m][a] = 0;
-        if (m < P.n_maps) {
-          const int64_t stride = a ? P.map[m].stride1 : P.map[m].stride0, len = a ? P.map[m].len1 : P.map[m].len0;
-          const int64_t q = flat0 / stride, sq = step / stride;
-          r[m][a] = flat0 - q * stride, i[m][a] = (int32_t)(q % len);
-          sr[m][a] = step - sq * stride, si[m][a] = (int32_t)(sq % len);
-        }
-      }
-    }
-  }
-  __device__ __forceinline__ int32_t cell(const FitParams& P, int m) const {
-    return i[m][0] * (int32_t)P.map[m].len1 + i[m][1];
-  }
-  __device__ __forceinline__ void next(const FitParams& P) {
-#pragma unroll
-    for (int m = 0; m < LZQ_FIT_MAX_MAPS; ++m) {
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        if (m < P.n_maps) {
-          const int64_t stride = a ? P.map[m].stride1 : P.map[m].stride0;
-          const int32_t len = (int32_t)(a ? P.map[m].len1 : P.map[m].len0);
-          r[m][a] += sr[m][a];
-          const bool carry = r[m][a] >= stride;
-          r[m][a] -= carry ? stride : 0;
-          i[m][a] += si[m][a] + (int32_t)carry;
-          i[m][a] -= i[m][a] >= len ? len : 0;
-        }
-      }
-    }
-  }
-};
-
-__device__ __forceinline__ uint64_t wave_min(uint64_t v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) {
-    const uint64_t o = __shfl_xor((unsigned long long)v, s);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_max(uint64_t v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) {
-    const uint64_t o = __shfl_xor((unsigned long long)v, s);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor((unsigned long long)v, s);
-  return v;
-}
-
-enum { OP_MIN = 0, OP_MAX = 1, OP_SUM = 2 };
-// one value per thread -> one per block, in thread 0 (red: kFitWaves words of LDS)
-template <int OP>
-__device__ __forceinline__ uint64_t block_reduce(uint64_t v, uint64_t* red) {
-  v = OP == OP_MIN ? wave_min(v) : OP == OP_MAX ? wave_max(v) : wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint64_t r = red[0];
-  for (int w = 1; w < kFitWaves; ++w) {
-    const uint64_t o = red[w];
-    r = OP == OP_MIN ? (o < r ? o : r) : OP == OP_MAX ? (o > r ? o : r) : r + o;
-  }
-  return r;
-}
-
 __device__ __forceinline__ uint64_t gmin(uint64_t* p, uint64_t v) {
   return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void gadd(uint64_t* p, uint64_t v) {
-  if (v) __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ uint64_t gload(const uint64_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -475,7 +343,7 @@ __global__ void __launch_bounds__(kFitBlock) fit_sel_scatter_kernel(const lzq_yi
 using lzq::FitParams;
 
 // host-side validation of a fit's terms, levels and maps into the kernels' parameter block
-static int fit_params(const char* who, const lzq_fit_term* terms, int32_t n_terms, const double* levels,
+int lzq_fit_params(const char* who, const lzq_fit_term* terms, int32_t n_terms, const double* levels,
                       int32_t n_levels, const lzq_fit_map* maps, int32_t n_maps, FitParams* P, int64_t* words) {
   char msg[256];
 #define FIT_FAIL(...) (snprintf(msg, sizeof msg, __VA_ARGS__), lzq_set_error(LZQ_EINVAL, msg))
@@ -527,7 +395,7 @@ static int fit_params(const char* who, const lzq_fit_term* terms, int32_t n_term
 #undef FIT_FAIL
 }
 
-static int fit_launched(const char* who) {
+int lzq_fit_launched(const char* who) {
   const hipError_t e = hipGetLastError();
   if (e == hipSuccess) return LZQ_OK;
   char msg[256];
@@ -545,19 +413,19 @@ extern "C" {
 int64_t lzq_fit_state_bytes(const lzq_fit_map* maps, int32_t n_maps) {
   FitParams P;
   int64_t words = 0;
-  const int rc = fit_params("lzq_fit_state_bytes", nullptr, 0, nullptr, 0, maps, n_maps, &P, &words);
+  const int rc = lzq_fit_params("lzq_fit_state_bytes", nullptr, 0, nullptr, 0, maps, n_maps, &P, &words);
   return rc != LZQ_OK ? rc : words * 8;
 }
 
 int lzq_fit_reset(const lzq_fit_map* maps, int32_t n_maps, void* d_state, void* stream) {
   FitParams P;
   int64_t words = 0;
-  const int rc = fit_params("lzq_fit_reset", nullptr, 0, nullptr, 0, maps, n_maps, &P, &words);
+  const int rc = lzq_fit_params("lzq_fit_reset", nullptr, 0, nullptr, 0, maps, n_maps, &P, &words);
   if (rc != LZQ_OK) return rc;
   if (!d_state) return lzq_set_error(LZQ_EINVAL, "lzq_fit_reset: bad arguments (null state)");
   hipLaunchKernelGGL(lzq::fit_reset_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (uint64_t*)d_state, words, P);
-  return fit_launched("lzq_fit_reset");
+  return lzq_fit_launched("lzq_fit_reset");
 }
 
 int lzq_fit_update(const lzq_fit_term* terms, int32_t n_terms, const double* levels, int32_t n_levels,
@@ -566,7 +434,7 @@ int lzq_fit_update(const lzq_fit_term* terms, int32_t n_terms, const double* lev
   FitParams P;
   int64_t words = 0;
   if (!terms) return lzq_set_error(LZQ_EINVAL, "lzq_fit_update: bad arguments (null terms)");
-  const int rc = fit_params("lzq_fit_update", terms, n_terms, levels, n_levels, maps, n_maps, &P, &words);
+  const int rc = lzq_fit_params("lzq_fit_update", terms, n_terms, levels, n_levels, maps, n_maps, &P, &words);
   if (rc != LZQ_OK) return rc;
   if (start < 0 || count < 0 || start > LZQ_FIT_MAX_INDEX - count || !d_state || (count > 0 && !d_yields))
     return lzq_set_error(LZQ_EINVAL, "lzq_fit_update: bad arguments (start, count >= 0, start + count <= 2^62, "
@@ -582,7 +450,7 @@ int lzq_fit_update(const lzq_fit_term* terms, int32_t n_terms, const double* lev
     hipLaunchKernelGGL(lzq::fit_min_kernel<false>, grid, block, 0, st, d_yields, start, count, S, P);
     hipLaunchKernelGGL(lzq::fit_idx_kernel<false>, grid, block, 0, st, d_yields, start, count, S, P);
   }
-  return fit_launched("lzq_fit_update");
+  return lzq_fit_launched("lzq_fit_update");
 }
 
 int lzq_fit_select(const lzq_fit_term* terms, int32_t n_terms, double level, const lzq_yield* d_yields, int64_t start,
@@ -590,7 +458,7 @@ int lzq_fit_select(const lzq_fit_term* terms, int32_t n_terms, double level, con
   FitParams P;
   int64_t words = 0;
   if (!terms) return lzq_set_error(LZQ_EINVAL, "lzq_fit_select: bad arguments (null terms)");
-  const int rc = fit_params("lzq_fit_select", terms, n_terms, nullptr, 0, nullptr, 0, &P, &words);
+  const int rc = lzq_fit_params("lzq_fit_select", terms, n_terms, nullptr, 0, nullptr, 0, &P, &words);
   if (rc != LZQ_OK) return rc;
   if (isnan(level)) return lzq_set_error(LZQ_EINVAL, "lzq_fit_select: level is NaN");
   if (start < 0 || count < 0 || start > LZQ_FIT_MAX_INDEX - count || cap < 0 || !d_state || (count > 0 && !d_yields) ||
@@ -620,7 +488,7 @@ int lzq_fit_select(const lzq_fit_term* terms, int32_t n_terms, double level, con
       hipLaunchKernelGGL(lzq::fit_sel_scatter_kernel<false>, grid, block, 0, st, d_yields, start, count, level, counts,
                          nb, d_selected, cap, P);
   }
-  const int rl = fit_launched("lzq_fit_select");
+  const int rl = lzq_fit_launched("lzq_fit_select");
   e = hipFreeAsync(counts, st);
   if (rl != LZQ_OK) return rl;
   if (e != hipSuccess) return lzq_set_error(LZQ_EHIP, hipGetErrorString(e));
@@ -630,14 +498,14 @@ int lzq_fit_select(const lzq_fit_term* terms, int32_t n_terms, double level, con
 int lzq_fit_merge(const lzq_fit_map* maps, int32_t n_maps, void* d_dst, const void* d_src, void* stream) {
   FitParams P;
   int64_t words = 0;
-  const int rc = fit_params("lzq_fit_merge", nullptr, 0, nullptr, 0, maps, n_maps, &P, &words);
+  const int rc = lzq_fit_params("lzq_fit_merge", nullptr, 0, nullptr, 0, maps, n_maps, &P, &words);
   if (rc != LZQ_OK) return rc;
   if (!d_dst || !d_src || d_dst == d_src)
     return lzq_set_error(LZQ_EINVAL, "lzq_fit_merge: bad arguments (two distinct non-null states)");
   const int64_t items = LZQ_FIT_HEADER_WORDS + (words - LZQ_FIT_HEADER_WORDS) / 2;
   hipLaunchKernelGGL(lzq::fit_merge_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (uint64_t*)d_dst, (const uint64_t*)d_src, items, P);
-  return fit_launched("lzq_fit_merge");
+  return lzq_fit_launched("lzq_fit_merge");
 }
 
 }  // extern "C"

@@ -324,6 +324,49 @@ class Engine:
                 sel = state.sel[:min(int(words[_fit.W_SEL_TOTAL]), state.fit.select[1])].cpu().numpy()
         return _fit.HostFit.from_words(state.fit, state.maps, words, sel).result()
 
+    # -- sweep posteriors (lzq_post_*; fit.HostPosterior is the numpy implementation) ---------
+    def post_state(self, fit, maps, offset: float) -> "PostState":
+        """An empty device-resident posterior state for `fit`, its resolved maps and `offset`
+        (finite, >= 0: a row weighs exp(-(chi2 - offset) / 2))."""
+        st = PostState(fit, maps, offset)
+        nbytes = self.lib.lzq_post_state_bytes(st.c_maps, len(st.maps))
+        if nbytes < 0:
+            self._check(int(nbytes))
+        st.words = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.lzq_post_reset(st.c_maps, len(st.maps), _vp(st.words), self._stream()))
+        return st
+
+    def post_update(self, state: "PostState", yields: torch.Tensor, start: int) -> None:
+        """Fold the records of flat grid indices [start, start + n) into `state`, asynchronously on
+        the current stream.  The rows a state has taken are counted here, on the host: beyond 2^32
+        its 64-bit sums would no longer be exact."""
+        y = self._fit_rows(yields)
+        state.count(y.shape[0])
+        with torch.cuda.device(self.device):
+            self._check(self.lib.lzq_post_update(state.c_terms, len(state.fit.terms), state.c_levels,
+                                                 len(state.fit.levels), state.c_maps, len(state.maps), state.offset,
+                                                 _vp(y), int(start), y.shape[0], _vp(state.words), self._stream()))
+
+    def post_merge(self, state: "PostState", words: torch.Tensor, rows: Optional[int] = None) -> None:
+        """state <- state + another state of the same layout and offset (its words, from any device;
+        `rows`: how many rows it holds, read from its counts when not given)."""
+        w = words.to(device=self.device, dtype=torch.int64).contiguous()
+        if w.numel() != state.words.numel():
+            raise ValueError("post_merge: states of different layouts")
+        state.count(int(w[:4].sum()) if rows is None else int(rows))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.lzq_post_merge(state.c_maps, len(state.maps), _vp(state.words), _vp(w),
+                                                self._stream()))
+        w.record_stream(torch.cuda.current_stream(self.device))
+
+    def post_result(self, state: "PostState", axis_values: Optional[dict] = None) -> dict:
+        """The posterior as host values (fit.HostPosterior.result's dictionary): the one
+        device-to-host read of the state."""
+        from . import fit as _fit
+        return _fit.HostPosterior.from_words(state.fit, state.maps, state.offset, state.words.cpu().numpy(),
+                                             axis_values).result()
+
     # -- ODE fallback (fpy:200-219, 270-286, 385-417) ---------------------------------------
     def ode_params_to_device(self, recs: np.ndarray) -> torch.Tensor:
         """lzq_ode_params records (numpy ODE_DTYPE array) -> device byte tensor (Engine.ode's
@@ -765,6 +808,23 @@ class FitState:
             self.c_maps[k].n_axes = len(m.axes)
             for a in range(len(m.axes)):
                 self.c_maps[k].stride[a], self.c_maps[k].len[a] = m.stride[a], m.len[a]
+
+
+class PostState(FitState):
+    """A posterior's device-resident state (Engine.post_state): `words` (int64, include/lzq.h
+    "posterior state"), its offset, and the number of rows folded in so far."""
+
+    def __init__(self, fit, maps, offset: float):
+        super().__init__(fit, maps)
+        self.offset = float(offset)
+        if not (np.isfinite(self.offset) and self.offset >= 0):
+            raise ValueError(f"posterior offset must be finite and >= 0, got {offset!r}")
+        self.rows = 0
+
+    def count(self, n: int) -> None:
+        if self.rows + n > _native.POST_MAX_ROWS:
+            raise ValueError(f"a posterior state takes at most 2^32 rows (exact 64-bit sums), got {self.rows + n}")
+        self.rows += n
 
 
 class ProfileShapes:

@@ -21,7 +21,10 @@ Fits (--fit FILE | paper; fit.py): every chunk, computed or resumed, is also fol
 stream into a device-resident fit state (chi2 to targets: counts within levels, best point, profile
 maps, selection; lzq_fit_*), the ranks' fixed-size states are all-gathered and merged in rank order,
 and rank 0 writes fit.json, fit_maps.npz and selected.npy.  --no-table keeps only that: chunks pass
-through two chunk-sized buffers, with no shard, no all-gather and no table.npy.
+through two chunk-sized buffers, with no shard, no all-gather and no table.npy.  A fit spec with a
+"posterior" key adds the likelihood-weighted sums (lzq_post_*: evidence, mass within levels, credible
+thresholds, marginal maps) as a "posterior" block of fit.json and map<k>_posterior / map<k>_weight
+arrays of fit_maps.npz; its offset "best" takes a second pass over the table, so not with --no-table.
 
     python -m <package>.sweep --spec C2 --out sweep_c2          # 1 GPU
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m <package>.sweep --spec C4 --out c4
@@ -590,7 +593,9 @@ def run_sweep(spec: SweepSpec, engine=None, rank: int = 0, world: int = 1, chunk
     acc = None
     if fit is not None:
         from . import fit as _fit
-        acc = _fit.make_accumulator(fit, fit.resolve(spec), engine)
+        if not keep_table and fit.posterior is not None and fit.posterior["offset"] == "best":
+            raise ValueError(_fit.NO_TABLE_BEST)
+        acc = _fit.make_accumulator(fit, fit.resolve(spec), engine, fit.axis_values(spec))
     elif not keep_table:
         raise ValueError("keep_table=False needs a fit")
     local = run_local(compute, start, end,
@@ -601,7 +606,7 @@ def run_sweep(spec: SweepSpec, engine=None, rank: int = 0, world: int = 1, chunk
     table = gather_table(local, spec.total, rank, world, group) if keep_table else None
     if acc is None:
         return table
-    return table, _fit.combine(acc, world, group)
+    return table, _fit.combine(acc, world, group, local=local, start=start)
 
 
 def coherent_P(spec: SweepSpec, s: int, n: int, engine):
@@ -727,7 +732,7 @@ def main(argv=None):
                     help="nccl (= RCCL over xGMI, default) | gloo (rehearsal: several ranks on one GPU)")
     ap.add_argument("--fit", default=None, metavar="FILE|paper",
                     help="fit the yields to targets on the device, chunk by chunk: a fit-spec JSON (terms, levels, "
-                         "maps, select; see fit.py), or `paper`: Y_B = 8.72e-11 and DM_over_B = 5.357, each with "
+                         "maps, select, posterior; see fit.py), or `paper`: Y_B = 8.72e-11 and DM_over_B = 5.357, each with "
                          "sigma at 1%% of its target (nominal tolerances, not measurement errors).  Writes fit.json, "
                          "fit_maps.npz, selected.npy and a \"fit\" block in summary.json")
     ap.add_argument("--no-table", action="store_true",
@@ -755,6 +760,8 @@ def main(argv=None):
         from . import fit as _fit
         fitspec = _fit.load(args.fit)
         fit_maps = fitspec.resolve(spec)
+        if args.no_table and fitspec.posterior is not None and fitspec.posterior["offset"] == "best":
+            ap.error("--no-table: " + _fit.NO_TABLE_BEST)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -776,14 +783,14 @@ def main(argv=None):
 
     compute = make_compute(spec, eng, reuse=args.reuse_zsums)
     make_out = lambda n: torch.empty((n, 6), dtype=torch.float64, device=eng.device)
-    acc = _fit.make_accumulator(fitspec, fit_maps, eng) if fitspec is not None else None
+    acc = _fit.make_accumulator(fitspec, fit_maps, eng, fitspec.axis_values(spec)) if fitspec is not None else None
     local = run_local(compute, start, end, make_out, args.chunk,
                       args.out, args.resume, sync=torch.cuda.synchronize,
                       log=(print if rank == 0 else (lambda s: None)), key=key, fit=acc,
                       keep_table=not args.no_table)
     ode_status = ode_status_summary(getattr(compute, "ode_status", None), None, eng.device)
     table = None if args.no_table else gather_table(local, spec_total, rank, world)
-    fit_result = _fit.combine(acc, world) if acc is not None else None
+    fit_result = _fit.combine(acc, world, local=local, start=start) if acc is not None else None
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     if rank == 0:

@@ -563,6 +563,60 @@ int lzq_fit_select(const lzq_fit_term* terms, int32_t n_terms, double level, con
  * combine of a sharded sweep. */
 int lzq_fit_merge(const lzq_fit_map* maps, int32_t n_maps, void* d_dst, const void* d_src, void* stream);
 
+/* ---- sweep posteriors: the likelihood-weighted half of a fit -------------- */
+/* The weight of a row with chi2 c (the fit's expression; the row is valid iff c is finite), for an
+ * offset (finite, >= 0) that is a parameter of the state: a = c - offset;
+ *   a < 0: the row is "above": counted in n_above, it carries no weight (with offset = the sweep's
+ *          best chi2 no valid row is above);
+ *   else   w = exp(-a/2) in (0, 1], computed as 2^(a K), K = -log2(e)/2: u = a K, kd = rint(u),
+ *          r = fma(a, K, -kd), w = ldexp(p(r), (int)kd) with p the degree-11 polynomial of 2^r
+ *          (0.63 ulp), every operation rounded on its own; q = min(trunc(w 2^62), 2^62) is the
+ *          weight in fixed point, units of 2^-62.  Rows with q = 0 (a >~ 124 ln 2 = 85.95) count in
+ *          n_zero; a >= 2048 is q = 0 without the evaluation (exp(-a/2) is no double from 1490 on,
+ *          and the reduction only holds while |u| < 2^52).
+ * Only IEEE operations and an exact truncation are used: host and device give the same q.
+ *
+ * Every accumulator is a PAIR of unsigned 64-bit words (hi, lo) = (sum of q >> 31, sum of
+ * q & 0x7fffffff), its value hi * 2^31 + lo in units of 2^-62.  All additions are integer, so the
+ * state is the same bit for bit for every order, chunking, sharding and merge tree -- exactly, as
+ * long as a state has been fed at most LZQ_POST_MAX_ROWS = 2^32 rows in all (merged states count
+ * together): each word then stays below 2^32 * 2^31 = 2^63.  The library cannot see that total
+ * across calls; the caller counts (the Python Engine does, and raises).
+ *
+ * The state is an array of 64-bit words, all 0 when empty:
+ *   [0] n_used: valid rows with a >= 0 and q > 0   [1] n_zero   [2] n_above   [3] n_invalid
+ *   [4,5] Z, the total weight   [6 + 2l, 7 + 2l] the weight of the rows with c <= levels[l], l < 4
+ *   [14..31] reserved (0)
+ *   [32 + 2b, 33 + 2b], b < LZQ_POST_BINS: the weight of the rows with min(2047, (int)(a * 16)) = b,
+ *       a histogram of weight by a in bins of 1/16 (the last bin takes everything beyond 127.94);
+ *       its sum is Z, and credible thresholds are read from it
+ *   then per map, in order, `cells` pairs: the marginal weight of each cell (lzq_fit_map's decode). */
+#define LZQ_POST_HEADER_WORDS 32
+#define LZQ_POST_BINS 2048
+#define LZQ_POST_MAX_ROWS ((int64_t)1 << 32) /* rows folded into one state, merges included */
+/* q of n HOST rows into q_out: ~0 for an invalid row, ~0 - 1 for a row above, else the weight.  A
+ * plain host function (no GPU work): the definition the kernels are compared with. */
+int lzq_post_weights_host(const lzq_fit_term* terms, int32_t n_terms, double offset, const lzq_yield* rows, int64_t n,
+                          uint64_t* q_out);
+/* Bytes of the state for these maps ((LZQ_POST_HEADER_WORDS + 2 LZQ_POST_BINS + 2 cells per map)
+ * words of 8 B); negative: an error code.  Arguments are validated as lzq_fit_* validates them,
+ * with LZQ_EINVAL and a message before any GPU work; an offset that is negative or not finite is
+ * LZQ_EINVAL too. */
+int64_t lzq_post_state_bytes(const lzq_fit_map* maps, int32_t n_maps);
+/* The empty state (all words 0), asynchronously on `stream`. */
+int lzq_post_reset(const lzq_fit_map* maps, int32_t n_maps, void* d_state, void* stream);
+/* Fold records d_yields[count] of flat grid indices [start, start + count) into the state: one
+ * streaming pass; sums are taken inside a wave first, the histogram and maps of up to 1024 cells
+ * in all are block-private in LDS, larger maps go straight to global memory; the result does not
+ * depend on the path.  Every call on one state must pass the same offset.  Asynchronous on
+ * `stream`, no host synchronisation; count <= LZQ_POST_MAX_ROWS. */
+int lzq_post_update(const lzq_fit_term* terms, int32_t n_terms, const double* levels, int32_t n_levels,
+                    const lzq_fit_map* maps, int32_t n_maps, double offset, const lzq_yield* d_yields, int64_t start,
+                    int64_t count, void* d_state, void* stream);
+/* d_dst <- d_dst + d_src, word by word (two states of these maps and one offset over disjoint
+ * rows): the same result whatever the order of merges. */
+int lzq_post_merge(const lzq_fit_map* maps, int32_t n_maps, void* d_dst, const void* d_src, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
