@@ -46,11 +46,23 @@ class LzqFitMap(ctypes.Structure):  # struct lzq_fit_map
                 ("len", ctypes.c_int64 * 2)]
 
 
+class LzqObsAxis(ctypes.Structure):  # struct lzq_obs_axis
+    _fields_ = [("field", ctypes.c_int32), ("kind", ctypes.c_int32), ("lo", ctypes.c_double), ("hi", ctypes.c_double),
+                ("bins", ctypes.c_int32), ("log2_sub", ctypes.c_int32)]
+
+
+class LzqObs(ctypes.Structure):  # struct lzq_obs
+    _fields_ = [("n_axes", ctypes.c_int32), ("reserved", ctypes.c_int32), ("axes", LzqObsAxis * 2)]
+
+
 assert ctypes.sizeof(LzqFitTerm) == 24 and ctypes.sizeof(LzqFitMap) == 40
+assert ctypes.sizeof(LzqObsAxis) == 32 and ctypes.sizeof(LzqObs) == 72
 FIT_MAX_TERMS = FIT_MAX_LEVELS = FIT_MAX_MAPS = 4  # LZQ_FIT_MAX_*
 FIT_MAX_CELLS = 1 << 24
 FIT_HEADER_WORDS = 32
 POST_HEADER_WORDS, POST_BINS, POST_MAX_ROWS = 32, 2048, 1 << 32  # LZQ_POST_*
+OBS_MAX, OBS_MAX_CELLS, OBS_LDS_CELLS, OBS_HEADER_WORDS = 4, 1 << 20, 1536, 4  # LZQ_OBS_*
+OBS_LINEAR, OBS_LOG2 = 0, 1
 
 AOV_FIELDS = ("I_p", "beta_over_H", "T_p_GeV", "v_w", "g_star")
 
@@ -143,7 +155,8 @@ EXPORTS = ("lzq_abi_version", "lzq_last_error", "lzq_init", "lzq_zgrid_init", "l
            "lzq_ode_aov_T", "lzq_ode_rhs", "lzq_profile_splines", "lzq_profile_crossings",
            "lzq_lz_propagate_profile",
            "lzq_fit_state_bytes", "lzq_fit_reset", "lzq_fit_update", "lzq_fit_select", "lzq_fit_merge",
-           "lzq_post_weights_host", "lzq_post_state_bytes", "lzq_post_reset", "lzq_post_update", "lzq_post_merge")
+           "lzq_post_weights_host", "lzq_post_state_bytes", "lzq_post_reset", "lzq_post_update", "lzq_post_merge",
+           "lzq_obs_state_bytes", "lzq_obs_reset", "lzq_obs_update", "lzq_obs_merge", "lzq_obs_cells_host")
 # the lzq_point fields an ODE spline table depends on (A/V kernel fpy:141-156 + window fpy:368-369)
 ODE_TABLE_KEY = ("I_p", "beta_over_H", "T_p_GeV", "v_w", "g_star", "T_min_over_Tp", "T_max_over_Tp")
 # the lzq_point fields the quadrature's z-sums depend on (its y-grid and c; lzq_yields_batch_reuse)
@@ -225,12 +238,18 @@ def load(path: str | None = None):
     L.lzq_post_reset.argtypes = [P(LzqFitMap), i32, vp, vp]
     L.lzq_post_update.argtypes = [P(LzqFitTerm), i32, P(d), i32, P(LzqFitMap), i32, d, vp, i64, i64, vp, vp]
     L.lzq_post_merge.argtypes = [P(LzqFitMap), i32, vp, vp, vp]
+    L.lzq_obs_state_bytes.argtypes = [P(LzqObs), i32]
+    L.lzq_obs_reset.argtypes = [P(LzqObs), i32, vp, vp]
+    L.lzq_obs_update.argtypes = [P(LzqFitTerm), i32, P(LzqObs), i32, i32, d, vp, i64, vp, vp]
+    L.lzq_obs_merge.argtypes = [P(LzqObs), i32, vp, vp, vp]
+    L.lzq_obs_cells_host.argtypes = [P(LzqObs), i32, i32, vp, i64, vp]
     for name in EXPORTS:
         if name not in ("lzq_abi_version", "lzq_last_error"):
             getattr(L, name).restype = ctypes.c_int
     L.lzq_sweep_grid_reuse_workspace.restype = ctypes.c_int64
     L.lzq_fit_state_bytes.restype = ctypes.c_int64
     L.lzq_post_state_bytes.restype = ctypes.c_int64
+    L.lzq_obs_state_bytes.restype = ctypes.c_int64
     if path is None:
         _lib = L
     return L

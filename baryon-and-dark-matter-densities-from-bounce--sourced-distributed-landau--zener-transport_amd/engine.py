@@ -367,6 +367,50 @@ class Engine:
         return _fit.HostPosterior.from_words(state.fit, state.maps, state.offset, state.words.cpu().numpy(),
                                              axis_values).result()
 
+    # -- sweep observables (lzq_obs_*; fit.HostObservables is the numpy implementation) -------
+    def obs_state(self, fit, observables, offset: Optional[float] = None) -> "ObsState":
+        """An empty device-resident observable state for `fit` and its observables
+        (fit.Observable); offset None: unweighted (counts and chi2 minima only), else rows weigh
+        exp(-(chi2 - offset) / 2) as the posterior's."""
+        st = ObsState(fit, observables, offset)
+        nbytes = self.lib.lzq_obs_state_bytes(st.c_obs, len(st.observables))
+        if nbytes < 0:
+            self._check(int(nbytes))
+        st.words = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.lzq_obs_reset(st.c_obs, len(st.observables), _vp(st.words), self._stream()))
+        return st
+
+    def obs_update(self, state: "ObsState", yields: torch.Tensor) -> None:
+        """Fold records into `state`, asynchronously on the current stream.  The rows a state has
+        taken are counted here, on the host: beyond 2^32 its 64-bit sums would no longer be exact."""
+        y = self._fit_rows(yields)
+        state.count(y.shape[0])
+        with torch.cuda.device(self.device):
+            self._check(self.lib.lzq_obs_update(state.c_terms, len(state.fit.terms), state.c_obs,
+                                                len(state.observables), int(state.offset is not None),
+                                                state.offset or 0.0, _vp(y), y.shape[0], _vp(state.words),
+                                                self._stream()))
+
+    def obs_merge(self, state: "ObsState", words: torch.Tensor, rows: Optional[int] = None) -> None:
+        """state <- state merged with another state of the same layout and offset (its words, from
+        any device; `rows`: how many rows it holds, read from its counts when not given)."""
+        w = words.to(device=self.device, dtype=torch.int64).contiguous()
+        if w.numel() != state.words.numel():
+            raise ValueError("obs_merge: states of different layouts")
+        state.count(int(w[:3].sum()) if rows is None else int(rows))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.lzq_obs_merge(state.c_obs, len(state.observables), _vp(state.words), _vp(w),
+                                               self._stream()))
+        w.record_stream(torch.cuda.current_stream(self.device))
+
+    def obs_result(self, state: "ObsState", z_units: Optional[int] = None) -> list:
+        """The observables as host values (fit.HostObservables.result's list): the one
+        device-to-host read of the state."""
+        from . import fit as _fit
+        return _fit.HostObservables.from_words(state.fit, state.observables, state.offset,
+                                               state.words.cpu().numpy()).result(z_units)
+
     # -- ODE fallback (fpy:200-219, 270-286, 385-417) ---------------------------------------
     def ode_params_to_device(self, recs: np.ndarray) -> torch.Tensor:
         """lzq_ode_params records (numpy ODE_DTYPE array) -> device byte tensor (Engine.ode's
@@ -824,6 +868,27 @@ class PostState(FitState):
     def count(self, n: int) -> None:
         if self.rows + n > _native.POST_MAX_ROWS:
             raise ValueError(f"a posterior state takes at most 2^32 rows (exact 64-bit sums), got {self.rows + n}")
+        self.rows += n
+
+
+class ObsState:
+    """The observables' device-resident state (Engine.obs_state): `words` (int64, include/lzq.h
+    "sweep observables"), the offset (None: unweighted) and the number of rows folded in so far."""
+
+    def __init__(self, fit, observables, offset: Optional[float] = None):
+        from . import fit as _fit
+        self.fit, self.observables = fit, list(observables)
+        self.offset = None if offset is None else float(offset)
+        if self.offset is not None and not (np.isfinite(self.offset) and self.offset >= 0):
+            raise ValueError(f"observables: the offset must be finite and >= 0, got {offset!r}")
+        self.words: Optional[torch.Tensor] = None
+        self.c_terms = FitState(fit, []).c_terms
+        self.c_obs = _fit.obs_structs(self.observables)
+        self.rows = 0
+
+    def count(self, n: int) -> None:
+        if self.rows + n > _native.POST_MAX_ROWS:
+            raise ValueError(f"an observable state takes at most 2^32 rows (exact 64-bit sums), got {self.rows + n}")
         self.rows += n
 
 

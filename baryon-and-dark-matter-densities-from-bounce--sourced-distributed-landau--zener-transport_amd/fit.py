@@ -27,6 +27,24 @@ offset is folded chunk by chunk behind the fit; "best" (the default) is the comb
 chi2 and takes a second pass over the rank's shard, so it needs the table.  HostPosterior is the
 numpy implementation (weights from the library's host function lzq_post_weights_host, integer
 sums in numpy); Engine.post_* drive the HIP kernel (lzq_post_update).
+
+The optional top-level key "observables" describes the OUTPUTS: a list of 0..4 histograms over one
+or two yield fields,
+
+    "observables": [{"axes": [{"field": "DM_over_B", "lo": 0.01, "hi": 1000.0, "per_octave": 8}]},
+                    {"axes": [{"field": "Y_B", "lo": 0.0, "hi": 2e-10, "bins": 200},
+                              {"field": "DM_over_B", "lo": 0.0, "hi": 10.0, "bins": 100}],
+                     "quantiles": [0.16, 0.5, 0.84]}]
+
+"bins" makes an axis linear, "per_octave" (1, 2, .. 256) binary-logarithmic: its bins are the
+exponent and the leading mantissa bits of the value, so sub-bins are linear inside an octave and
+no logarithm is taken.  Per cell the state (include/lzq.h, "sweep observables") holds the number
+of valid rows, their smallest chi2 (the profile likelihood of the field) and, with a posterior,
+their weight: a third device-resident state, folded behind the fit's (and with the offset "best"
+in the posterior's second pass), with the same independence of chunking, sharding and world
+size.  HostObservables is the numpy implementation, written from the definition;
+Engine.obs_* drive the HIP kernel (lzq_obs_update).  "quantiles" (1-D observables with weight;
+default 0.025, 0.16, 0.5, 0.84, 0.975) are read from the cumulated weights in exact integers.
 """
 from __future__ import annotations
 
@@ -51,6 +69,10 @@ PW_MAPS = POST_HEADER_WORDS + 2 * POST_BINS
 POST_UNIT = 1 << 62                      # the weight of a row at the offset
 Q_INVALID, Q_ABOVE = (1 << 64) - 1, (1 << 64) - 2   # lzq_post_weights_host's sentinels
 DEFAULT_CREDIBLE = (0.683, 0.954, 0.997)
+OBS_MAX, OBS_MAX_CELLS = _native.OBS_MAX, _native.OBS_MAX_CELLS
+OBS_LDS_CELLS, OBS_HEADER_WORDS = _native.OBS_LDS_CELLS, _native.OBS_HEADER_WORDS
+OBS_OUT, OBS_NONFINITE = -1, -2          # lzq_obs_cells_host's classes of a row without a cell
+DEFAULT_QUANTILES = (0.025, 0.16, 0.5, 0.84, 0.975)
 NO_TABLE_BEST = ('a posterior with offset "best" takes a second pass over the table, which --no-table does not '
                  'keep: give a number as "offset"')
 # word offsets of the state (include/lzq.h)
@@ -91,10 +113,164 @@ class FitMap:
         return c
 
 
+def _obs_number(x, what: str) -> float:
+    if isinstance(x, (bool, str)) or not isinstance(x, (int, float)) or not math.isfinite(x):
+        raise ValueError(f"fit observables: {what} must be a finite number, got {x!r}")
+    return float(x)
+
+
+@dataclass(frozen=True)
+class ObsAxis:
+    """One axis of an observable over a yield field: linear (`bins`) or binary-logarithmic
+    (`per_octave` = 2^s sub-bins per octave).  The bin of a value is include/lzq.h's definition."""
+    field: str
+    lo: float
+    hi: float
+    bins: Optional[int] = None
+    per_octave: Optional[int] = None
+
+    def __post_init__(self):
+        if self.field not in YIELD_FIELDS:
+            raise ValueError(f"fit observables: unknown field {self.field!r} (one of {YIELD_FIELDS})")
+        lo, hi = _obs_number(self.lo, "lo"), _obs_number(self.hi, "hi")
+        if not lo < hi:
+            raise ValueError(f"fit observables: axis {self.field} needs lo < hi, got {lo!r}, {hi!r}")
+        if (self.bins is None) == (self.per_octave is None):
+            raise ValueError(f'fit observables: axis {self.field} takes exactly one of "bins" and "per_octave"')
+        if self.bins is not None:
+            if isinstance(self.bins, bool) or not isinstance(self.bins, int) or not 1 <= self.bins <= OBS_MAX_CELLS:
+                raise ValueError(f"fit observables: axis {self.field}: bins is an integer in 1..2^20, "
+                                 f"got {self.bins!r}")
+            with np.errstate(all="ignore"):
+                inv = np.float64(self.bins) / (np.float64(hi) - np.float64(lo))
+            if not (np.isfinite(inv) and inv > 0):
+                raise ValueError(f"fit observables: axis {self.field}: bins / (hi - lo) must be finite and > 0")
+        else:
+            po = self.per_octave
+            if isinstance(po, bool) or not isinstance(po, int) or po not in (1, 2, 4, 8, 16, 32, 64, 128, 256):
+                raise ValueError(f"fit observables: axis {self.field}: per_octave is a power of two in 1..256, "
+                                 f"got {po!r}")
+            if not lo > 0:
+                raise ValueError(f"fit observables: a logarithmic axis ({self.field}) needs lo > 0, got {lo!r}")
+            if self.n_bins < 1:
+                raise ValueError(f"fit observables: axis {self.field}: no sub-bin edge between lo and hi")
+        object.__setattr__(self, "lo", lo)
+        object.__setattr__(self, "hi", hi)
+
+    @property
+    def log(self) -> bool:
+        return self.per_octave is not None
+
+    @property
+    def log2_sub(self) -> int:
+        return int(self.per_octave).bit_length() - 1
+
+    def _key(self, x) -> np.ndarray:
+        """bits(x) >> (52 - s) of positive doubles."""
+        return (np.asarray(x, dtype=np.float64).view(np.uint64) >> np.uint64(52 - self.log2_sub)).astype(np.int64)
+
+    @property
+    def n_bins(self) -> int:
+        if not self.log:
+            return int(self.bins)
+        return int(self._key([self.hi])[0] - self._key([self.lo])[0])
+
+    @property
+    def inv(self) -> np.float64:
+        return np.float64(self.bins) / (np.float64(self.hi) - np.float64(self.lo))
+
+    def bin(self, x: np.ndarray) -> np.ndarray:
+        """The bin of each value (int64), OBS_OUT below or above the range; non-finite values are
+        the caller's (Observable.cell)."""
+        x = np.asarray(x, dtype=np.float64)
+        b = np.full(x.shape, OBS_OUT, dtype=np.int64)
+        fin = np.isfinite(x)
+        if self.log:
+            m = fin & (x > 0.0)
+            k = self._key(x[m]) - self._key([self.lo])[0]
+            b[m] = np.where((k >= 0) & (k < self.n_bins), k, OBS_OUT)
+        else:
+            m = fin & (x >= self.lo) & (x < self.hi)
+            t = (x[m] - np.float64(self.lo)) * self.inv        # two roundings, as the kernel's
+            b[m] = np.minimum(self.bins - 1, t.astype(np.int64))
+        return b
+
+    def edges(self) -> np.ndarray:
+        """The n_bins + 1 bin edges.  A logarithmic axis starts at lo rounded DOWN to a sub-bin edge
+        (and ends at hi rounded down to one): the edges the bins really have."""
+        e = np.arange(self.n_bins + 1, dtype=np.int64)
+        if self.log:
+            return ((self._key([self.lo])[0] + e).astype(np.uint64) << np.uint64(52 - self.log2_sub)).view(np.float64)
+        out = np.float64(self.lo) + e * ((np.float64(self.hi) - np.float64(self.lo)) / np.float64(self.bins))
+        out[-1] = self.hi
+        return out
+
+    def to_json(self) -> dict:
+        d = {"field": self.field, "lo": self.lo, "hi": self.hi}
+        d.update({"per_octave": self.per_octave} if self.log else {"bins": self.bins})
+        return d
+
+
+@dataclass(frozen=True)
+class Observable:
+    """A histogram over one or two different yield fields; cell b0, or b0 * bins1 + b1."""
+    axes: Tuple[ObsAxis, ...]
+    quantiles: Tuple[float, ...] = DEFAULT_QUANTILES
+
+    def __post_init__(self):
+        if not 1 <= len(self.axes) <= 2 or len({a.field for a in self.axes}) != len(self.axes):
+            raise ValueError("fit observables: an observable has one or two axes over different fields")
+        if self.cells > OBS_MAX_CELLS:
+            raise ValueError(f"fit observables: {self.cells} cells (at most 2^20 an observable)")
+        q = self.quantiles
+        if any(not 0.0 < x < 1.0 for x in q) or any(b <= a for a, b in zip(q, q[1:])):
+            raise ValueError(f"fit observables: quantiles must be ascending and inside (0, 1), got {list(q)}")
+
+    @property
+    def shape(self) -> Tuple[int, ...]:
+        return tuple(a.n_bins for a in self.axes)
+
+    @property
+    def cells(self) -> int:
+        return int(np.prod(self.shape, dtype=np.int64))
+
+    def cell(self, rows: np.ndarray) -> np.ndarray:
+        """The class of (n, 6) records: the cell, OBS_OUT or OBS_NONFINITE (int64)."""
+        rows = np.asarray(rows, dtype=np.float64).reshape(-1, 6)
+        cols = [rows[:, YIELD_FIELDS.index(a.field)] for a in self.axes]
+        bins = [a.bin(x) for a, x in zip(self.axes, cols)]
+        cell = bins[0] if len(bins) == 1 else bins[0] * self.shape[1] + bins[1]
+        cell = np.where(np.logical_and.reduce([b >= 0 for b in bins]), cell, OBS_OUT)
+        return np.where(np.logical_and.reduce([np.isfinite(x) for x in cols]), cell, OBS_NONFINITE)
+
+    def to_json(self) -> dict:
+        return {"axes": [a.to_json() for a in self.axes], "quantiles": list(self.quantiles)}
+
+    @classmethod
+    def from_json(cls, d) -> "Observable":
+        if not isinstance(d, dict) or set(d) - {"axes", "quantiles"} or not isinstance(d.get("axes"), (list, tuple)):
+            raise ValueError(f'fit observables: an object with the keys "axes" (a list) and "quantiles", got {d!r}')
+        axes = []
+        for a in d["axes"]:
+            if not isinstance(a, dict) or set(a) - {"field", "lo", "hi", "bins", "per_octave"} or \
+                    not {"field", "lo", "hi"} <= set(a) or not isinstance(a["field"], str):
+                raise ValueError('fit observables: an axis is an object with "field", "lo", "hi" and one of "bins" and '
+                                 f'"per_octave", got {a!r}')
+            axes.append(ObsAxis(a["field"], a["lo"], a["hi"], a.get("bins"), a.get("per_octave")))
+        q = d.get("quantiles", DEFAULT_QUANTILES)
+        try:
+            q = tuple(float(x) for x in q)
+        except (TypeError, ValueError):
+            raise ValueError(f"fit observables: quantiles must be a list of fractions, got {q!r}") from None
+        return cls(tuple(axes), q)
+
+
 class FitSpec:
     def __init__(self, terms: Sequence[FitTerm], levels: Sequence[float] = (), maps: Sequence[Sequence[str]] = (),
-                 select: Optional[Tuple[float, int]] = None, posterior: Optional[dict] = None):
+                 select: Optional[Tuple[float, int]] = None, posterior: Optional[dict] = None,
+                 observables: Optional[Sequence] = None):
         self.posterior = self._posterior(posterior)
+        self.observables = self._observables(observables)
         self.terms = [t if isinstance(t, FitTerm) else FitTerm(*t) for t in terms]
         self.levels = [float(x) for x in levels]
         self.maps = [tuple(m) for m in maps]
@@ -142,9 +318,19 @@ class FitSpec:
             raise ValueError(f"fit posterior: credible fractions must be ascending and inside (0, 1), got {cred}")
         return {"offset": off, "credible": cred}
 
+    @staticmethod
+    def _observables(obs) -> List[Observable]:
+        if obs is None:
+            return []
+        if not isinstance(obs, (list, tuple)):
+            raise ValueError(f"fit observables: a list of at most {OBS_MAX} observables, got {obs!r}")
+        if len(obs) > OBS_MAX:
+            raise ValueError(f"fit observables: at most {OBS_MAX} observables, got {len(obs)}")
+        return [o if isinstance(o, Observable) else Observable.from_json(o) for o in obs]
+
     @classmethod
     def from_json(cls, d: dict) -> "FitSpec":
-        unknown = set(d) - {"terms", "levels", "maps", "select", "posterior"}
+        unknown = set(d) - {"terms", "levels", "maps", "select", "posterior", "observables"}
         if unknown:
             raise ValueError(f"unknown fit-spec keys {sorted(unknown)}")
         try:
@@ -154,7 +340,7 @@ class FitSpec:
             maps = [[m] if isinstance(m, str) else list(m) for m in d.get("maps", [])]
         except (KeyError, TypeError) as e:
             raise ValueError(f"malformed fit spec: {e!r}") from None
-        return cls(terms, d.get("levels", []), maps, select, d.get("posterior"))
+        return cls(terms, d.get("levels", []), maps, select, d.get("posterior"), d.get("observables"))
 
     def to_json(self) -> dict:
         d = {"terms": [{"field": t.field, "target": t.target, "sigma": t.sigma} for t in self.terms],
@@ -163,6 +349,8 @@ class FitSpec:
             d["select"] = {"level": self.select[0], "cap": self.select[1]}
         if self.posterior is not None:
             d["posterior"] = {"offset": self.posterior["offset"], "credible": list(self.posterior["credible"])}
+        if self.observables:
+            d["observables"] = [o.to_json() for o in self.observables]
         return d
 
     def axis_values(self, sweep_spec) -> dict:
@@ -556,6 +744,185 @@ def post_differences(a: dict, b: dict) -> List[str]:
     return out
 
 
+# ---- observables: histograms over yield fields ------------------------------------------------
+_INF_BITS = np.uint64(0x7FF0000000000000)
+
+
+def obs_state_words(observables: Sequence[Observable]) -> int:
+    return sum(OBS_HEADER_WORDS + 4 * o.cells for o in observables)
+
+
+def obs_structs(observables: Sequence[Observable]):
+    """The observables as the C ABI's lzq_obs array (at least one element, so it is never NULL)."""
+    arr = (_native.LzqObs * max(1, len(observables)))()
+    for k, o in enumerate(observables):
+        arr[k].n_axes = len(o.axes)
+        for a, ax in enumerate(o.axes):
+            c = arr[k].axes[a]
+            c.field, c.kind, c.lo, c.hi = YIELD_FIELDS.index(ax.field), int(ax.log), ax.lo, ax.hi
+            c.bins, c.log2_sub = (0, ax.log2_sub) if ax.log else (ax.bins, 0)
+    return arr
+
+
+def obs_cells_host(observables: Sequence[Observable], k: int, rows) -> np.ndarray:
+    """The classes of (n, 6) records in observable k from the library's host build of the one
+    definition (lzq_obs_cells_host; no GPU is touched): what Observable.cell is compared with."""
+    rows = np.ascontiguousarray(np.asarray(rows, dtype=np.float64).reshape(-1, 6))
+    out = np.empty(rows.shape[0], dtype=np.int32)
+    lib = _native.load()
+    _native.check(lib.lzq_obs_cells_host(obs_structs(observables), len(observables), int(k), rows.ctypes.data,
+                                         rows.shape[0], out.ctypes.data), lib)
+    return out
+
+
+class HostObservables:
+    """The observable state in numpy: `w`, the uint64 words of include/lzq.h's "sweep observables".
+    offset None: unweighted (counts and chi2 minima only); else rows weigh as the posterior's."""
+
+    def __init__(self, fit: FitSpec, observables: Sequence[Observable], offset: Optional[float] = None):
+        self.fit, self.observables = fit, list(observables)
+        self.offset = None if offset is None else float(offset)
+        if self.offset is not None and not (math.isfinite(self.offset) and self.offset >= 0):
+            raise ValueError(f"observables: the offset must be finite and >= 0, got {offset!r}")
+        if len(self.observables) > OBS_MAX:
+            raise ValueError(f"observables: at most {OBS_MAX}, got {len(self.observables)}")
+        self.w = np.zeros(obs_state_words(self.observables), dtype=np.uint64)
+        for off, o in self._offsets():
+            self.w[off + OBS_HEADER_WORDS + 3 * o.cells:off + OBS_HEADER_WORDS + 4 * o.cells] = _INF_BITS
+        self.rows = 0    # rows folded in, merges included: the exact sums hold up to POST_MAX_ROWS
+
+    def _offsets(self):
+        off = 0
+        for o in self.observables:
+            yield off, o
+            off += OBS_HEADER_WORDS + 4 * o.cells
+
+    def _count(self, n: int) -> None:
+        if self.rows + n > POST_MAX_ROWS:
+            raise ValueError(f"an observable state takes at most 2^32 rows (exact 64-bit sums), got {self.rows + n}")
+        self.rows += n
+
+    def update(self, rows) -> None:
+        rows = np.asarray(rows, dtype=np.float64).reshape(-1, 6)
+        n = rows.shape[0]
+        if n == 0:
+            return
+        self._count(n)
+        c = chi2_rows(self.fit, rows)
+        valid = np.isfinite(c)
+        if self.offset is not None:
+            q = post_weights(self.fit, self.offset, rows)
+            has = valid & (q >= np.uint64(1)) & (q <= np.uint64(POST_UNIT))
+            hi, lo = q >> np.uint64(31), q & np.uint64(0x7FFFFFFF)
+        w = self.w
+        for off, o in self._offsets():
+            cell = o.cell(rows)
+            w[off] += np.uint64(int((valid & (cell >= 0)).sum()))
+            w[off + 1] += np.uint64(int((valid & (cell == OBS_OUT)).sum()))
+            w[off + 2] += np.uint64(int((valid & (cell == OBS_NONFINITE)).sum()))
+            m = valid & (cell >= 0)
+            base = off + OBS_HEADER_WORDS
+            np.add.at(w, base + 2 * o.cells + cell[m], np.uint64(1))
+            np.minimum.at(w, base + 3 * o.cells + cell[m], c[m].view(np.uint64))   # chi2 >= 0 orders like its bits
+            if self.offset is not None:
+                mw = m & has
+                np.add.at(w, base + 2 * cell[mw], hi[mw])
+                np.add.at(w, base + 2 * cell[mw] + 1, lo[mw])
+
+    def _chi2_mask(self) -> np.ndarray:
+        is_chi2 = np.zeros(self.w.size, dtype=bool)
+        for off, o in self._offsets():
+            is_chi2[off + OBS_HEADER_WORDS + 3 * o.cells:off + OBS_HEADER_WORDS + 4 * o.cells] = True
+        return is_chi2
+
+    def merge(self, o: "HostObservables") -> None:
+        """Fold in the state of other (disjoint) rows: words add, the chi2 words take the minimum."""
+        if o.offset != self.offset or o.w.size != self.w.size:
+            raise ValueError("observables merge: states of different offsets or layouts")
+        self._count(o.rows)
+        self.w = np.where(self._chi2_mask(), np.minimum(self.w, o.w), self.w + o.w)
+
+    def to_words(self) -> np.ndarray:
+        return self.w.view(np.int64).copy()
+
+    @classmethod
+    def from_words(cls, fit: FitSpec, observables: Sequence[Observable], offset: Optional[float],
+                   words) -> "HostObservables":
+        w = np.ascontiguousarray(np.asarray(words), dtype=np.int64).reshape(-1)
+        s = cls(fit, observables, offset)
+        if w.size != s.w.size:
+            raise ValueError(f"observable state of {w.size} words, expected {s.w.size} for these observables")
+        s.w = w.view(np.uint64).copy()
+        s.rows = int(sum(int(x) for x in s.w[:3])) if s.observables else 0   # the valid rows: what the sums hold
+        return s
+
+    def result(self, z_units: Optional[int] = None) -> List[dict]:
+        """Host values of the state, one dictionary an observable.  As HostPosterior.result, everything
+        is derived from the exact integers in a fixed order.  z_units: the posterior's Z in units of
+        2^-62 (its "Z_units"), for the share of Z that fell inside each observable's range."""
+        out = []
+        for off, o in self._offsets():
+            w, base = self.w, off + OBS_HEADER_WORDS
+            pairs = w[base:base + 2 * o.cells].reshape(o.cells, 2).copy()
+            val = (pairs[:, 0].astype(object) << 31) + pairs[:, 1].astype(object)   # exact Python integers
+            total = int(val.sum()) if o.cells else 0
+            # a cell's weight as a float: hi * 2^31 is exact below 2^84, the sum rounds once
+            wf = pairs[:, 0].astype(np.float64) * 2.0 ** 31 + pairs[:, 1].astype(np.float64)
+            post = (wf / np.float64(total) if total else np.full(o.cells, np.nan)).reshape(o.shape)
+            res = {"axes": [a.to_json() for a in o.axes], "edges": [a.edges() for a in o.axes],
+                   "weighted": self.offset is not None, "offset": self.offset,
+                   "n_in": int(w[off]), "n_out": int(w[off + 1]), "n_nonfinite": int(w[off + 2]),
+                   "count": w[base + 2 * o.cells:base + 3 * o.cells].astype(np.int64).reshape(o.shape),
+                   "chi2_min": w[base + 3 * o.cells:base + 4 * o.cells].view(np.float64).reshape(o.shape).copy(),
+                   "weight": pairs, "posterior": post, "total_units": str(total),
+                   "in_range_share": (total / z_units if z_units else None), "quantiles": None, "mode": None}
+            if len(o.axes) == 1 and self.offset is not None:
+                e = res["edges"][0]
+                span = lambda b: {"bin": int(b), "lo": float(e[b]), "hi": float(e[b + 1])}
+                qs = []
+                cum = np.cumsum(val) if total else None
+                for p in o.quantiles:
+                    entry = {"p": p, "bin": None, "lo": None, "hi": None}
+                    if total:
+                        fp = Fraction(p)    # exact: the first bin with cum * den >= num * total, in integers
+                        entry.update(span(int(np.argmax((cum * fp.denominator >= fp.numerator * total).astype(bool)))))
+                    qs.append(entry)
+                res["quantiles"] = qs
+                if total:
+                    res["mode"] = span(int(np.argmax((val == val.max()).astype(bool))))    # the lowest such bin
+            out.append(res)
+        return out
+
+
+def obs_differences(a: Sequence[dict], b: Sequence[dict]) -> List[str]:
+    """Where two observable results differ (exact integers, floats by bits); empty when equal."""
+    out = []
+    bits = lambda x: np.asarray(x, dtype=np.float64).view(np.int64)
+    if len(a) != len(b):
+        return ["number of observables"]
+    for k, (oa, ob) in enumerate(zip(a, b)):
+        for key in ("axes", "weighted", "offset", "n_in", "n_out", "n_nonfinite", "total_units", "in_range_share",
+                    "quantiles", "mode"):
+            if oa[key] != ob[key]:
+                out.append(f"observable {k}: {key}: {oa[key]} != {ob[key]}")
+        if oa["count"].shape != ob["count"].shape:
+            out.append(f"observable {k}: shape")
+            continue
+        if any(not np.array_equal(bits(x), bits(y)) for x, y in zip(oa["edges"], ob["edges"])):
+            out.append(f"observable {k}: edges")
+        if not np.array_equal(oa["count"], ob["count"]):
+            out.append(f"observable {k}: count differs in {int((oa['count'] != ob['count']).sum())} cells")
+        if not np.array_equal(bits(oa["chi2_min"]), bits(ob["chi2_min"])):
+            out.append(f"observable {k}: chi2_min differs in "
+                       f"{int((bits(oa['chi2_min']) != bits(ob['chi2_min'])).sum())} cells")
+        if not np.array_equal(oa["weight"], ob["weight"]):
+            n = int((oa["weight"] != ob["weight"]).any(axis=1).sum())
+            out.append(f"observable {k}: weight differs in {n} cells")
+        elif not np.array_equal(bits(oa["posterior"]), bits(ob["posterior"])):
+            out.append(f"observable {k}: posterior")
+    return out
+
+
 # ---- accumulators: what the sweep driver folds chunks into -----------------------------------
 class HostAccumulator:
     """Chunks of CPU records (the gloo tests, any host table) into a HostFit."""
@@ -564,20 +931,45 @@ class HostAccumulator:
         self.fit, self.maps, self.axis_values = fit, list(maps), axis_values
         self.host = HostFit(fit, maps)
         self.post = None    # a numeric posterior offset is folded chunk by chunk; "best" after the combine
+        self.obs = None     # observables: unweighted without a posterior, else begun with it
         if fit.posterior is not None and fit.posterior["offset"] != "best":
             self.post_begin(fit.posterior["offset"])
+        elif fit.posterior is None and fit.observables:
+            self.obs = HostObservables(fit, fit.observables, None)
 
     def update(self, rows, start: int) -> None:
         rows = rows.detach().numpy() if hasattr(rows, "detach") else rows
         self.host.update(rows, start)
         if self.post is not None:
             self.post.update(rows, start)
+        if self.obs is not None:
+            self.obs.update(rows)
 
     def post_begin(self, offset: float) -> None:
         self.post = HostPosterior(self.fit, self.maps, offset, self.axis_values)
+        if self.fit.observables:
+            self.obs = HostObservables(self.fit, self.fit.observables, offset)
 
     def post_update(self, rows, start: int) -> None:
-        self.post.update(rows.detach().cpu().numpy() if hasattr(rows, "detach") else rows, start)
+        rows = rows.detach().cpu().numpy() if hasattr(rows, "detach") else rows
+        self.post.update(rows, start)
+        if self.obs is not None:
+            self.obs.update(rows)
+
+    def obs_words(self):
+        import torch
+        return torch.from_numpy(self.obs.to_words())
+
+    def obs_result(self, z_units: Optional[int] = None) -> List[dict]:
+        return self.obs.result(z_units)
+
+    def obs_merged(self, words, z_units: Optional[int] = None) -> List[dict]:
+        """The result of the ranks' observable states `words` [world, n] merged."""
+        import torch
+        tot = HostObservables(self.fit, self.fit.observables, self.obs.offset)
+        for w in torch.as_tensor(words).cpu().numpy():
+            tot.merge(HostObservables.from_words(self.fit, self.fit.observables, self.obs.offset, w))
+        return tot.result(z_units)
 
     def post_words(self):
         import torch
@@ -624,8 +1016,11 @@ class DeviceAccumulator:
         self.fit, self.maps, self.engine, self.axis_values = fit, list(maps), engine, axis_values
         self.state = engine.fit_state(fit, maps)
         self.post = None
+        self.obs = None
         if fit.posterior is not None and fit.posterior["offset"] != "best":
             self.post_begin(fit.posterior["offset"])
+        elif fit.posterior is None and fit.observables:
+            self.obs = engine.obs_state(fit, fit.observables, None)
 
     def update(self, rows, start: int) -> None:
         self.engine.fit_update(self.state, rows, start)
@@ -633,12 +1028,30 @@ class DeviceAccumulator:
             self.engine.fit_select(self.state, rows, start)
         if self.post is not None:   # right behind the fit, on the same stream
             self.engine.post_update(self.post, rows, start)
+        if self.obs is not None:
+            self.engine.obs_update(self.obs, rows)
 
     def post_begin(self, offset: float) -> None:
         self.post = self.engine.post_state(self.fit, self.maps, offset)
+        if self.fit.observables:
+            self.obs = self.engine.obs_state(self.fit, self.fit.observables, offset)
 
     def post_update(self, rows, start: int) -> None:
         self.engine.post_update(self.post, rows, start)
+        if self.obs is not None:
+            self.engine.obs_update(self.obs, rows)
+
+    def obs_words(self):
+        return self.obs.words
+
+    def obs_result(self, z_units: Optional[int] = None) -> List[dict]:
+        return self.engine.obs_result(self.obs, z_units)
+
+    def obs_merged(self, words, z_units: Optional[int] = None) -> List[dict]:
+        tot = self.engine.obs_state(self.fit, self.fit.observables, self.obs.offset)
+        for w in words:
+            self.engine.obs_merge(tot, w)
+        return self.engine.obs_result(tot, z_units)
 
     def post_words(self):
         return self.post.words
@@ -712,7 +1125,22 @@ def combine(acc, world: int = 1, group=None, local=None, start: int = 0) -> dict
     res = _combine_fit(acc, group)
     if acc.fit.posterior is not None:
         res["posterior"] = combine_posterior(acc, res, local, start, group)
+    if acc.fit.observables:
+        res["observables"] = combine_observables(acc, res, group)
     return res
+
+
+def combine_observables(acc, res: dict, group=None) -> List[dict]:
+    """The observables of the whole grid on every rank: the ranks' states (folded behind the fit, or
+    with the offset "best" in the posterior's second pass, which combine_posterior has run) are
+    all-gathered and merged.  The posterior's Z (`res`) gives each range's share of it."""
+    import torch.distributed as dist
+    z = int(res["posterior"]["Z_units"]) if res.get("posterior") is not None else None
+    if not (dist.is_available() and dist.is_initialized()):
+        return acc.obs_result(z)
+    w = acc.obs_words()
+    src = (w if dist.get_backend(group) == "nccl" else w.cpu()).contiguous()
+    return acc.obs_merged(_gather_words(src, dist.get_world_size(group), group), z)
 
 
 def _combine_fit(acc, group=None) -> dict:
@@ -781,12 +1209,20 @@ def report(fit: FitSpec, result: dict, sweep_spec, n_points: int, best_yields: O
         rep["posterior"] = {**{k: p[k] for k in ("offset", "n_used", "n_zero", "n_above", "n_invalid", "Z", "Z_units",
                                                  "mass_within", "credible")},
                             "maps": [{"axes": m["axes"], "mean": m["mean"], "std": m["std"]} for m in p["maps"]]}
+    if result.get("observables"):
+        rep["observables"] = [{**{k: o[k] for k in ("axes", "weighted", "offset", "n_in", "n_out", "n_nonfinite",
+                                                    "total_units", "in_range_share", "quantiles", "mode")},
+                               "shape": list(o["count"].shape),
+                               "range": [[float(e[0]), float(e[-1])] for e in o["edges"]],   # (log axes: rounded down)
+                               "chi2_min": (float(o["chi2_min"].min()) if o["n_in"] else None)}
+                              for o in result["observables"]]
     return rep
 
 
 def write_files(out_dir: str, rep: dict, result: dict) -> None:
     """fit.json, fit_maps.npz (map<k>_chi2_min / map<k>_argmin; with a posterior map<k>_posterior and
-    map<k>_weight, the (cells, 2) uint64 pairs) and selected.npy in `out_dir`."""
+    map<k>_weight, the (cells, 2) uint64 pairs) and selected.npy in `out_dir`; with observables
+    fit_obs.npz (obs<k>_weight, _count, _chi2_min, _posterior and _edges<a> per axis)."""
     import os
     with open(os.path.join(out_dir, "fit.json"), "w") as f:
         json.dump(rep, f, indent=2)
@@ -799,3 +1235,11 @@ def write_files(out_dir: str, rep: dict, result: dict) -> None:
     np.savez(os.path.join(out_dir, "fit_maps.npz"), **arrays)
     sel = result["selected"] if result["selected"] is not None else np.empty(0, dtype=np.int64)
     np.save(os.path.join(out_dir, "selected.npy"), np.asarray(sel, dtype=np.int64), allow_pickle=False)
+    if result.get("observables"):
+        arrays = {}
+        for k, o in enumerate(result["observables"]):
+            for name in ("weight", "count", "chi2_min", "posterior"):
+                arrays[f"obs{k}_{name}"] = o[name]
+            for a, e in enumerate(o["edges"]):
+                arrays[f"obs{k}_edges{a}"] = e
+        np.savez(os.path.join(out_dir, "fit_obs.npz"), **arrays)

@@ -25,6 +25,11 @@ through two chunk-sized buffers, with no shard, no all-gather and no table.npy. 
 "posterior" key adds the likelihood-weighted sums (lzq_post_*: evidence, mass within levels, credible
 thresholds, marginal maps) as a "posterior" block of fit.json and map<k>_posterior / map<k>_weight
 arrays of fit_maps.npz; its offset "best" takes a second pass over the table, so not with --no-table.
+An "observables" key adds histograms over one or two yield fields (lzq_obs_*: per cell the count of
+valid rows, the smallest chi2 and, with a posterior, the weight; quantiles and the mode of 1-D ones)
+as an "observables" block of fit.json and a file fit_obs.npz.  They are folded behind the fit --
+unweighted without a posterior, weighted with a numeric offset, both of which work with --no-table --
+or, with the offset "best", in the posterior's second pass.
 
     python -m <package>.sweep --spec C2 --out sweep_c2          # 1 GPU
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m <package>.sweep --spec C4 --out c4
@@ -732,9 +737,10 @@ def main(argv=None):
                     help="nccl (= RCCL over xGMI, default) | gloo (rehearsal: several ranks on one GPU)")
     ap.add_argument("--fit", default=None, metavar="FILE|paper",
                     help="fit the yields to targets on the device, chunk by chunk: a fit-spec JSON (terms, levels, "
-                         "maps, select, posterior; see fit.py), or `paper`: Y_B = 8.72e-11 and DM_over_B = 5.357, each with "
-                         "sigma at 1%% of its target (nominal tolerances, not measurement errors).  Writes fit.json, "
-                         "fit_maps.npz, selected.npy and a \"fit\" block in summary.json")
+                         "maps, select, posterior, observables; see fit.py), or `paper`: Y_B = 8.72e-11 and DM_over_B = 5.357, "
+                         "each with sigma at 1%% of its target (nominal tolerances, not measurement errors).  Writes "
+                         "fit.json, fit_maps.npz, selected.npy, with \"observables\" (histograms over yield fields) "
+                         "fit_obs.npz, and a \"fit\" block in summary.json")
     ap.add_argument("--no-table", action="store_true",
                     help="with --fit: keep only the fit -- chunks pass through two chunk-sized buffers, there is "
                          "no all-gather, no table.npy and no checkpoint (a grid larger than HBM or the disk)")

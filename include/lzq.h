@@ -617,6 +617,81 @@ int lzq_post_update(const lzq_fit_term* terms, int32_t n_terms, const double* le
  * rows): the same result whatever the order of merges. */
 int lzq_post_merge(const lzq_fit_map* maps, int32_t n_maps, void* d_dst, const void* d_src, void* stream);
 
+/* ---- sweep observables: histograms of a fit over yield fields ------------- */
+/* The fit and posterior states are indexed by the sweep's input axes; an OBSERVABLE is a histogram
+ * over one or two lzq_yield fields, folded from the same records on the same stream.  Per cell it
+ * keeps the number of valid rows, their smallest chi2 (a profile likelihood of the field) and, on
+ * a weighted call, their posterior weight q (lzq_post_update's, for the call's offset).
+ *
+ * The bin of a finite value x on an axis -- integer and IEEE operations only, each rounded on its
+ * own, so host and device agree:
+ *   LZQ_OBS_LINEAR (lo < hi finite, bins >= 1, inv = bins / (hi - lo) in float64, which must be
+ *     finite and > 0): below if x < lo, above if x >= hi, else min(bins - 1, (int64)((x - lo) * inv)).
+ *   LZQ_OBS_LOG2 (0 < lo < hi finite, 2^log2_sub sub-bins per octave, log2_sub in 0..8):
+ *     key(x) = bits(x) >> (52 - log2_sub) for x > 0 (sub-bins are linear inside an octave; no
+ *     logarithm is taken); bins = key(hi) - key(lo) >= 1; the bin is key(x) - key(lo); below if
+ *     x <= 0 or key(x) < key(lo), above if key(x) >= key(hi).  Edge e is the double with bits
+ *     (key(lo) + e) << (52 - log2_sub): the effective range is [lo, hi) rounded down to sub-bin edges.
+ * Every VALID row (finite chi2) falls into one class per observable: NONFINITE if one of the
+ * observable's fields is NaN or +-inf; else OUT if one is below or above; else IN cell b0, or
+ * b0 * bins1 + b1 for two axes.  Invalid rows touch nothing (the fit counts them).
+ *
+ * The state is an array of 64-bit words; per observable, in order:
+ *   4 header words: n_in, n_out, n_nonfinite, reserved (0)
+ *   2 * cells words: the weight of each cell as a pair (hi, lo) = (sum of q >> 31, sum of
+ *       q & 0x7fffffff), exactly the posterior state's pairs; added only on a weighted call and only
+ *       for rows that carry weight (1 <= q <= 2^62)
+ *   cells words: the count of valid rows in the cell (weightless and "above" rows included)
+ *   cells words: the smallest chi2 in the cell as a double's bits (+inf: empty), again over every
+ *       valid row of the cell
+ * There is no argmin: it would take the fit's second pass, and lzq_fit_select already lists the
+ * points.  All sums are integer and the minimum is an integer minimum (chi2 >= 0 orders like its
+ * bits), so the state is the same bit for bit for every order, chunking, sharding and merge tree,
+ * up to LZQ_POST_MAX_ROWS rows a state, merges included (the caller counts, as for the posterior). */
+#define LZQ_OBS_MAX 4
+#define LZQ_OBS_MAX_CELLS (1 << 20) /* per observable */
+#define LZQ_OBS_LDS_CELLS 1536      /* observables of up to this many cells IN ALL stay block-private in LDS */
+#define LZQ_OBS_HEADER_WORDS 4
+#define LZQ_OBS_LINEAR 0
+#define LZQ_OBS_LOG2 1
+typedef struct lzq_obs_axis {
+  int32_t field;    /* 0..5: the doubles of lzq_yield in declaration order */
+  int32_t kind;     /* LZQ_OBS_LINEAR or LZQ_OBS_LOG2 */
+  double lo, hi;
+  int32_t bins;     /* LZQ_OBS_LINEAR: the number of bins; LZQ_OBS_LOG2: ignored */
+  int32_t log2_sub; /* LZQ_OBS_LOG2: 0..8; LZQ_OBS_LINEAR: ignored */
+} lzq_obs_axis;     /* 32 bytes */
+typedef struct lzq_obs {
+  int32_t n_axes;   /* 1 or 2, over different fields */
+  int32_t reserved; /* 0 */
+  lzq_obs_axis axes[2];
+} lzq_obs;          /* 72 bytes */
+
+/* Observables are host arrays.  LZQ_EINVAL (with a message, before any GPU work) for more than
+ * LZQ_OBS_MAX observables, an axis count other than 1 or 2, an unknown field or kind, two axes over
+ * one field, a range or bin count outside the rules above, and more than LZQ_OBS_MAX_CELLS cells. */
+/* Bytes of the state ((4 + 4 cells) words of 8 B per observable); negative: an error code. */
+int64_t lzq_obs_state_bytes(const lzq_obs* obs, int32_t n_obs);
+/* The empty state (zeros, +inf in the chi2 words), asynchronously on `stream`. */
+int lzq_obs_reset(const lzq_obs* obs, int32_t n_obs, void* d_state, void* stream);
+/* Fold records d_yields[count] into the state: one streaming pass.  weighted != 0 adds the rows'
+ * weights for `offset` (finite, >= 0; the same for every weighted call on a state); weighted == 0
+ * leaves the weight words alone and ignores offset.  Nothing depends on a row's flat index, so
+ * there is no `start`.  The lanes of a wave that share a cell are combined before anything leaves
+ * the wave; observables of up to LZQ_OBS_LDS_CELLS cells in all are block-private in LDS, larger
+ * ones go straight to global memory; the result does not depend on the path.  Asynchronous on
+ * `stream`, no host synchronisation; count <= LZQ_POST_MAX_ROWS. */
+int lzq_obs_update(const lzq_fit_term* terms, int32_t n_terms, const lzq_obs* obs, int32_t n_obs, int32_t weighted,
+                   double offset, const lzq_yield* d_yields, int64_t count, void* d_state, void* stream);
+/* d_dst <- d_dst merged with d_src (two states of these observables over disjoint rows): words
+ * add, the chi2 words take the minimum. */
+int lzq_obs_merge(const lzq_obs* obs, int32_t n_obs, void* d_dst, const void* d_src, void* stream);
+/* The class of n HOST rows in observable k into cell_out: the cell, -1 for OUT, -2 for NONFINITE
+ * (validity is not looked at: there are no terms).  A plain host function (no GPU work): the
+ * definition the kernel is compared with. */
+int lzq_obs_cells_host(const lzq_obs* obs, int32_t n_obs, int32_t k, const lzq_yield* rows, int64_t n,
+                       int32_t* cell_out);
+
 #ifdef __cplusplus
 }
 #endif
