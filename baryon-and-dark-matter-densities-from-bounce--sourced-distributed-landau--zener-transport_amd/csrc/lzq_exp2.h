@@ -121,7 +121,9 @@ LZQ_HD double exp2_nonpos(double c2, double g, int32_t bias = 0) {
 //    13   2sq  64 KB     1.73e-14 (78 ulp)   9          5.25e5  (default: completed square, below)
 // The 13-bit address is ONE v_lshlrev_b16 ((k << 3) mod 2^16 = 8*(k mod 8192)).  The default's
 // 1.73e-14 bound moves Y_B by at most that much (relative), 6e5 x inside the north_star 1e-8
-// gate; tests/test_exp2_host.py pins every row against mpmath.
+// gate; tests/test_exp2_host.py pins every row against mpmath on the host, and
+// tests/test_gpu_zsum.py the device's sums F and A/V (LDS table, SDWA address, exponent insert)
+// against a 60-digit sum with a tolerance built on that bound.
 #ifndef LZQ_TABBITS
 #define LZQ_TABBITS 13
 #endif
@@ -172,7 +174,9 @@ struct TabPoly<14, 3> {
 // (A = 11818: 2.16e-14) -- 6e5 x inside the north_star 1e-8 gate (tests/test_exp2_host.py
 // pins it against mpmath).  C ~ 2^-27.06 lowers the table's exponents by 28, so KMIN is
 // -1506 N (e + 512 - 28 >= -1022 keeps T''*2^(e+512) normal); those clamped nodes still
-// contribute omega*2^u with u < -1506 octaves, which rounds away exactly.
+// contribute omega*2^u with u < -1506 octaves, which rounds away exactly (clamp onset sampled
+// densely against mpmath in tests/test_gpu_zsum.py; a clamp constant that leaves the normal range
+// is one of the defects tests/test_zsum_host.py shows that comparison to reject).
 #ifndef LZQ_SQFORM
 #define LZQ_SQFORM 1
 #endif

@@ -403,12 +403,16 @@ __device__ __forceinline__ void zsum(const ZNode* __restrict__ zt, const double*
 // constant reduction is inexact; every such node has u < KMIN, takes the clamped path (the
 // clamp-free test below sees it), and its term omega' * T''(KMIN) * ((A + O(|u| 2^-52))^2 + beta)
 // stays below 2^-1074 for |u| < 2^200, so it rounds away exactly like the underflow it stands
-// for (tests/test_exp2_host.py); build_ztable bounds |u| by that on the host.
+// for; build_ztable bounds |u| by that on the host.  Pinned by tests/test_gpu_zsum.py: A/V on the
+// (2400, 30) and (12000, 30) grids, whose live lanes reach |u| >= 2^51, against mpmath up to the
+// dead threshold, and equal bits for equal y whatever the wave holds (dead, clamped, clamp-free).
 //
 // truncate != 0 (lzq_tune LZQ_TUNE_TRUNCATE; NOT used by the headline bench, which is dense
 // per SURVEY §8d): the pass stops at kend, the first z-node (rounded up to the unroll) beyond
 // which every live lane has c2*g4_k < -1080 octaves.  Those nodes add omega*2^u < 2^-1080 to
-// F, which the accumulate's rounding discards exactly, so F is bit-identical to the dense sum.
+// F, which the accumulate's rounding discards exactly, so F is bit-identical to the dense sum
+// (tests/test_zsum_host.py in a one-lane model, every regime and padded grids; on the device
+// tests/test_gpu_zsum.py: truncated tables against dense kernels, per value and through Y_B).
 // (Needs g4 non-decreasing over the grid: the host passes truncate = 0 for a grid whose
 // rounded g4 is not.)
 template <int YB, int EXPV, int NZ = 0>
