@@ -13,7 +13,7 @@ import torch
 
 import logging
 
-from . import _native
+from . import _native, fit as _fit
 from .config import to_aov, to_ctypes_aov, to_ctypes_ode, to_ctypes_point, to_point
 
 _log = logging.getLogger("lzq")
@@ -259,157 +259,74 @@ class Engine:
         self._keepalive = dev_vals  # axis buffers must outlive the async launch
         return out
 
-    # -- sweep fits (lzq_fit_*; fit.py holds the spec and the numpy implementation) ------------
+    # -- sweep fits, posteriors, observables (lzq_fit_*, lzq_post_*, lzq_obs_*): forwards to the
+    # device-resident states below; fit.py holds the specs and the numpy implementations -------
     def fit_state(self, fit, maps, select: bool = True) -> "FitState":
         """An empty device-resident fit state for `fit` (fit.FitSpec) and its resolved maps
         (fit.FitSpec.resolve); select=False leaves out the selection list (a merge target)."""
-        st = FitState(fit, maps)
-        nbytes = self.lib.lzq_fit_state_bytes(st.c_maps, len(st.maps))
-        if nbytes < 0:
-            self._check(int(nbytes))
-        st.words = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)
-        if select and fit.select is not None:
-            st.sel = torch.empty(max(1, fit.select[1]), dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            self._check(self.lib.lzq_fit_reset(st.c_maps, len(st.maps), _vp(st.words), self._stream()))
-        return st
-
-    def _fit_rows(self, yields: torch.Tensor) -> torch.Tensor:
-        if yields.dtype != torch.float64 or yields.dim() != 2 or yields.shape[1] != 6:
-            raise ValueError("fit: records are an (n, 6) float64 tensor in YIELD_FIELDS order")
-        return yields.to(self.device).contiguous()
+        return FitState(self, fit, maps, select)
 
     def fit_update(self, state: "FitState", yields: torch.Tensor, start: int) -> None:
         """Fold the records of flat grid indices [start, start + n) into `state`, asynchronously on
         the current stream."""
-        y = self._fit_rows(yields)
-        with torch.cuda.device(self.device):
-            self._check(self.lib.lzq_fit_update(state.c_terms, len(state.fit.terms), state.c_levels,
-                                                len(state.fit.levels), state.c_maps, len(state.maps), _vp(y),
-                                                int(start), y.shape[0], _vp(state.words), self._stream()))
+        state.update(yields, start, select=False)
 
     def fit_select(self, state: "FitState", yields: torch.Tensor, start: int) -> None:
         """Append the flat indices of the rows within fit.select's level to the state's list (kept
         ascending by feeding chunks in ascending order); no host synchronisation."""
-        if state.fit.select is None or state.sel is None:
-            raise ValueError("fit_select: the fit has no selection")
-        y = self._fit_rows(yields)
-        level, cap = state.fit.select
-        with torch.cuda.device(self.device):
-            self._check(self.lib.lzq_fit_select(state.c_terms, len(state.fit.terms), level, _vp(y), int(start),
-                                                y.shape[0], _vp(state.words), _vp(state.sel), int(cap),
-                                                self._stream()))
+        state.select(yields, start)
 
     def fit_merge(self, state: "FitState", words: torch.Tensor) -> None:
         """state <- state merged with another state of the same layout (its words, from any device)."""
-        w = words.to(device=self.device, dtype=torch.int64).contiguous()
-        if w.numel() != state.words.numel():
-            raise ValueError("fit_merge: states of different layouts")
-        with torch.cuda.device(self.device):
-            self._check(self.lib.lzq_fit_merge(state.c_maps, len(state.maps), _vp(state.words), _vp(w),
-                                               self._stream()))
-        w.record_stream(torch.cuda.current_stream(self.device))
+        state.merge_words(words)
 
     def fit_result(self, state: "FitState", selected: Optional[torch.Tensor] = None) -> dict:
         """The fit as host values (fit.HostFit.result's dictionary): the one device-to-host read of
         the state, and of the kept part of the selection list (or `selected`, a list assembled
         elsewhere)."""
-        from . import fit as _fit
-        words = state.words.cpu().numpy()
-        sel = None
-        if state.fit.select is not None:
-            if selected is not None:
-                sel = selected.cpu().numpy()
-            elif state.sel is not None:
-                sel = state.sel[:min(int(words[_fit.W_SEL_TOTAL]), state.fit.select[1])].cpu().numpy()
-        return _fit.HostFit.from_words(state.fit, state.maps, words, sel).result()
+        return state.result(selected)
 
-    # -- sweep posteriors (lzq_post_*; fit.HostPosterior is the numpy implementation) ---------
     def post_state(self, fit, maps, offset: float) -> "PostState":
         """An empty device-resident posterior state for `fit`, its resolved maps and `offset`
         (finite, >= 0: a row weighs exp(-(chi2 - offset) / 2))."""
-        st = PostState(fit, maps, offset)
-        nbytes = self.lib.lzq_post_state_bytes(st.c_maps, len(st.maps))
-        if nbytes < 0:
-            self._check(int(nbytes))
-        st.words = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            self._check(self.lib.lzq_post_reset(st.c_maps, len(st.maps), _vp(st.words), self._stream()))
-        return st
+        return PostState(self, fit, maps, offset)
 
     def post_update(self, state: "PostState", yields: torch.Tensor, start: int) -> None:
         """Fold the records of flat grid indices [start, start + n) into `state`, asynchronously on
         the current stream.  The rows a state has taken are counted here, on the host: beyond 2^32
         its 64-bit sums would no longer be exact."""
-        y = self._fit_rows(yields)
-        state.count(y.shape[0])
-        with torch.cuda.device(self.device):
-            self._check(self.lib.lzq_post_update(state.c_terms, len(state.fit.terms), state.c_levels,
-                                                 len(state.fit.levels), state.c_maps, len(state.maps), state.offset,
-                                                 _vp(y), int(start), y.shape[0], _vp(state.words), self._stream()))
+        state.update(yields, start)
 
     def post_merge(self, state: "PostState", words: torch.Tensor, rows: Optional[int] = None) -> None:
         """state <- state + another state of the same layout and offset (its words, from any device;
         `rows`: how many rows it holds, read from its counts when not given)."""
-        w = words.to(device=self.device, dtype=torch.int64).contiguous()
-        if w.numel() != state.words.numel():
-            raise ValueError("post_merge: states of different layouts")
-        state.count(int(w[:4].sum()) if rows is None else int(rows))
-        with torch.cuda.device(self.device):
-            self._check(self.lib.lzq_post_merge(state.c_maps, len(state.maps), _vp(state.words), _vp(w),
-                                                self._stream()))
-        w.record_stream(torch.cuda.current_stream(self.device))
+        state.merge_words(words, rows)
 
     def post_result(self, state: "PostState", axis_values: Optional[dict] = None) -> dict:
         """The posterior as host values (fit.HostPosterior.result's dictionary): the one
         device-to-host read of the state."""
-        from . import fit as _fit
-        return _fit.HostPosterior.from_words(state.fit, state.maps, state.offset, state.words.cpu().numpy(),
-                                             axis_values).result()
+        return state.result(axis_values)
 
-    # -- sweep observables (lzq_obs_*; fit.HostObservables is the numpy implementation) -------
     def obs_state(self, fit, observables, offset: Optional[float] = None) -> "ObsState":
         """An empty device-resident observable state for `fit` and its observables
         (fit.Observable); offset None: unweighted (counts and chi2 minima only), else rows weigh
         exp(-(chi2 - offset) / 2) as the posterior's."""
-        st = ObsState(fit, observables, offset)
-        nbytes = self.lib.lzq_obs_state_bytes(st.c_obs, len(st.observables))
-        if nbytes < 0:
-            self._check(int(nbytes))
-        st.words = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            self._check(self.lib.lzq_obs_reset(st.c_obs, len(st.observables), _vp(st.words), self._stream()))
-        return st
+        return ObsState(self, fit, observables, offset)
 
     def obs_update(self, state: "ObsState", yields: torch.Tensor) -> None:
-        """Fold records into `state`, asynchronously on the current stream.  The rows a state has
-        taken are counted here, on the host: beyond 2^32 its 64-bit sums would no longer be exact."""
-        y = self._fit_rows(yields)
-        state.count(y.shape[0])
-        with torch.cuda.device(self.device):
-            self._check(self.lib.lzq_obs_update(state.c_terms, len(state.fit.terms), state.c_obs,
-                                                len(state.observables), int(state.offset is not None),
-                                                state.offset or 0.0, _vp(y), y.shape[0], _vp(state.words),
-                                                self._stream()))
+        """Fold records into `state`, asynchronously on the current stream; counted as
+        post_update's."""
+        state.update(yields)
 
     def obs_merge(self, state: "ObsState", words: torch.Tensor, rows: Optional[int] = None) -> None:
         """state <- state merged with another state of the same layout and offset (its words, from
         any device; `rows`: how many rows it holds, read from its counts when not given)."""
-        w = words.to(device=self.device, dtype=torch.int64).contiguous()
-        if w.numel() != state.words.numel():
-            raise ValueError("obs_merge: states of different layouts")
-        state.count(int(w[:3].sum()) if rows is None else int(rows))
-        with torch.cuda.device(self.device):
-            self._check(self.lib.lzq_obs_merge(state.c_obs, len(state.observables), _vp(state.words), _vp(w),
-                                               self._stream()))
-        w.record_stream(torch.cuda.current_stream(self.device))
+        state.merge_words(words, rows)
 
     def obs_result(self, state: "ObsState", z_units: Optional[int] = None) -> list:
         """The observables as host values (fit.HostObservables.result's list): the one
         device-to-host read of the state."""
-        from . import fit as _fit
-        return _fit.HostObservables.from_words(state.fit, state.observables, state.offset,
-                                               state.words.cpu().numpy()).result(z_units)
+        return state.result(z_units)
 
     # -- ODE fallback (fpy:200-219, 270-286, 385-417) ---------------------------------------
     def ode_params_to_device(self, recs: np.ndarray) -> torch.Tensor:
@@ -834,62 +751,132 @@ def ode_step_counts_device(d_pts: torch.Tensor, n: int) -> torch.Tensor:
     return torch.where(ms > 0.0, torch.ceil(dx / ms), torch.full_like(dx, float("nan")))
 
 
-class FitState:
-    """A fit's device-resident state (Engine.fit_state): `words` (int64, include/lzq.h "fit state"),
-    `sel` (the selection list, int64[cap], or None) and the host structs of the C ABI."""
+class _SweepState:
+    """A device-resident sweep state (include/lzq.h): `words` (int64) and the host structs of the
+    C ABI.  It follows the protocol of fit.py's numpy states -- update(rows, start), words, like(),
+    merge_words(words), result(...) -- with allocation and reset, the merge and the read-back
+    written here once.  A kind gives KIND (its entry points are lzq_<KIND>_*), HOST (the numpy
+    state its words are read back into), `args` (what HOST, and after the engine the kind itself,
+    are constructed from), `layout` (the structs, and their number, that describe the words) and
+    its own update."""
+    KIND = HOST = None
 
-    def __init__(self, fit, maps):
-        self.fit, self.maps = fit, list(maps)
-        self.words: Optional[torch.Tensor] = None
-        self.sel: Optional[torch.Tensor] = None
-        self.c_terms = (_native.LzqFitTerm * len(fit.terms))()
-        for k, t in enumerate(fit.terms):
-            self.c_terms[k].field = YIELD_FIELDS.index(t.field)
-            self.c_terms[k].target, self.c_terms[k].sigma = t.target, t.sigma
-        self.c_levels = (ctypes.c_double * max(1, len(fit.levels)))(*fit.levels)
-        self.c_maps = (_native.LzqFitMap * max(1, len(self.maps)))()
-        for k, m in enumerate(self.maps):
-            self.c_maps[k].n_axes = len(m.axes)
-            for a in range(len(m.axes)):
-                self.c_maps[k].stride[a], self.c_maps[k].len[a] = m.stride[a], m.len[a]
+    def __init__(self, engine, args, layout, offset=None):
+        self.engine, self.fit, self.args, self.layout, self.offset = engine, args[0], args, layout, offset
+        self.c_terms, self.c_levels = _fit.term_structs(self.fit), _fit.level_array(self.fit)
+        self.rows = 0    # rows folded in, merges included (fit.count_rows; the fit's are not counted)
+        self._update = self._entry("update")
+        nbytes = self._entry("state_bytes")(*layout)
+        if nbytes < 0:
+            engine._check(int(nbytes))
+        self.words = torch.empty(nbytes // 8, dtype=torch.int64, device=engine.device)
+        self._launch(self._entry("reset"), *layout, _vp(self.words))
+
+    def _entry(self, name: str):
+        return getattr(self.engine.lib, f"lzq_{self.KIND}_{name}")
+
+    def _launch(self, entry, *args) -> None:
+        """entry(*args, stream) on the engine's device and the current stream."""
+        with torch.cuda.device(self.engine.device):
+            self.engine._check(entry(*args, self.engine._stream()))
+
+    def _records(self, yields: torch.Tensor) -> torch.Tensor:
+        if yields.dtype != torch.float64 or yields.dim() != 2 or yields.shape[1] != 6:
+            raise ValueError("fit: records are an (n, 6) float64 tensor in YIELD_FIELDS order")
+        return yields.to(self.engine.device).contiguous()
+
+    def like(self):
+        return type(self)(self.engine, *self.args)
+
+    def merge_words(self, words: torch.Tensor, rows: Optional[int] = None) -> None:
+        w = words.to(device=self.engine.device, dtype=torch.int64).contiguous()
+        if w.numel() != self.words.numel():
+            raise ValueError(f"{self.KIND}_merge: states of different layouts")
+        if self.HOST.COUNT_WORDS:
+            _fit.count_rows(self, int(w[:self.HOST.COUNT_WORDS].sum()) if rows is None else int(rows), self.HOST.WHAT)
+        self._launch(self._entry("merge"), *self.layout, _vp(self.words), _vp(w))
+        w.record_stream(torch.cuda.current_stream(self.engine.device))
+
+    def result(self, *args):
+        return self.HOST(*self.args).load(self.words.cpu().numpy()).result(*args)
 
 
-class PostState(FitState):
-    """A posterior's device-resident state (Engine.post_state): `words` (int64, include/lzq.h
-    "posterior state"), its offset, and the number of rows folded in so far."""
+class FitState(_SweepState):
+    """A fit's device-resident state (Engine.fit_state): `words` (include/lzq.h "fit state") and
+    `sel` (the selection list, int64[cap], or None)."""
+    KIND, HOST = "fit", _fit.HostFit
 
-    def __init__(self, fit, maps, offset: float):
-        super().__init__(fit, maps)
-        self.offset = float(offset)
-        if not (np.isfinite(self.offset) and self.offset >= 0):
-            raise ValueError(f"posterior offset must be finite and >= 0, got {offset!r}")
-        self.rows = 0
+    def __init__(self, engine, fit, maps, select: bool = True):
+        self.maps = list(maps)
+        self.c_maps = _fit.map_structs(self.maps)
+        super().__init__(engine, (fit, self.maps), (self.c_maps, len(self.maps)))
+        self.sel = None
+        if select and fit.select is not None:
+            self.sel = torch.empty(max(1, fit.select[1]), dtype=torch.int64, device=engine.device)
+        self._head = (self.c_terms, len(fit.terms), self.c_levels, len(fit.levels), *self.layout)
+        self._select = self._entry("select")
 
-    def count(self, n: int) -> None:
-        if self.rows + n > _native.POST_MAX_ROWS:
-            raise ValueError(f"a posterior state takes at most 2^32 rows (exact 64-bit sums), got {self.rows + n}")
-        self.rows += n
+    def like(self) -> "FitState":
+        return FitState(self.engine, *self.args, select=False)
+
+    def update(self, yields: torch.Tensor, start: int, select: bool = True) -> None:
+        """select: also append to the selection list, where the state has one."""
+        y = self._records(yields)
+        self._launch(self._update, *self._head, _vp(y), int(start), y.shape[0], _vp(self.words))
+        if select and self.sel is not None:
+            self.select(y, start)
+
+    def select(self, yields: torch.Tensor, start: int) -> None:
+        if self.sel is None:
+            raise ValueError("fit_select: the fit has no selection")
+        y = self._records(yields)
+        level, cap = self.fit.select
+        self._launch(self._select, self.c_terms, len(self.fit.terms), level, _vp(y), int(start), y.shape[0],
+                     _vp(self.words), _vp(self.sel), int(cap))
+
+    def kept(self) -> torch.Tensor:
+        """The kept part of the selection list (what a rank contributes to the combined one)."""
+        return self.sel[:min(int(self.words[_fit.W_SEL_TOTAL]), self.fit.select[1])]
+
+    def result(self, selected: Optional[torch.Tensor] = None) -> dict:
+        return super().result(self.kept() if selected is None and self.sel is not None else selected)
 
 
-class ObsState:
-    """The observables' device-resident state (Engine.obs_state): `words` (int64, include/lzq.h
-    "sweep observables"), the offset (None: unweighted) and the number of rows folded in so far."""
+class PostState(_SweepState):
+    """A posterior's device-resident state (Engine.post_state): `words` (include/lzq.h "posterior
+    state"), its offset, and the number of rows folded in so far."""
+    KIND, HOST = "post", _fit.HostPosterior
 
-    def __init__(self, fit, observables, offset: Optional[float] = None):
-        from . import fit as _fit
-        self.fit, self.observables = fit, list(observables)
-        self.offset = None if offset is None else float(offset)
-        if self.offset is not None and not (np.isfinite(self.offset) and self.offset >= 0):
-            raise ValueError(f"observables: the offset must be finite and >= 0, got {offset!r}")
-        self.words: Optional[torch.Tensor] = None
-        self.c_terms = FitState(fit, []).c_terms
+    def __init__(self, engine, fit, maps, offset: float):
+        self.maps = list(maps)
+        self.c_maps = _fit.map_structs(self.maps)
+        offset = _fit.check_offset(offset, "posterior")
+        super().__init__(engine, (fit, self.maps, offset), (self.c_maps, len(self.maps)), offset)
+        self._head = (self.c_terms, len(fit.terms), self.c_levels, len(fit.levels), *self.layout, offset)
+
+    def update(self, yields: torch.Tensor, start: int) -> None:
+        y = self._records(yields)
+        _fit.count_rows(self, y.shape[0], self.HOST.WHAT)
+        self._launch(self._update, *self._head, _vp(y), int(start), y.shape[0], _vp(self.words))
+
+
+class ObsState(_SweepState):
+    """The observables' device-resident state (Engine.obs_state): `words` (include/lzq.h "sweep
+    observables"), the offset (None: unweighted) and the number of rows folded in so far."""
+    KIND, HOST = "obs", _fit.HostObservables
+
+    def __init__(self, engine, fit, observables, offset: Optional[float] = None):
+        self.observables = list(observables)
         self.c_obs = _fit.obs_structs(self.observables)
-        self.rows = 0
+        offset = _fit.check_offset(offset, "observables", optional=True)
+        super().__init__(engine, (fit, self.observables, offset), (self.c_obs, len(self.observables)), offset)
+        self._head = (self.c_terms, len(fit.terms), *self.layout, int(offset is not None), offset or 0.0)
 
-    def count(self, n: int) -> None:
-        if self.rows + n > _native.POST_MAX_ROWS:
-            raise ValueError(f"an observable state takes at most 2^32 rows (exact 64-bit sums), got {self.rows + n}")
-        self.rows += n
+    def update(self, yields: torch.Tensor, start: int = 0) -> None:
+        """start: unused (a row's cell does not depend on its index); the states' common signature."""
+        y = self._records(yields)
+        _fit.count_rows(self, y.shape[0], self.HOST.WHAT)
+        self._launch(self._update, *self._head, _vp(y), y.shape[0], _vp(self.words))
 
 
 class ProfileShapes:

@@ -14,7 +14,9 @@ it is the same bit for bit however a sweep is cut into chunks, shards or ranks.
 
 HostFit is the plain numpy implementation (update, merge, result): the sweep driver uses it when
 the records are CPU tensors, and the GPU tests compare the HIP kernels (lzq_fit_*, through
-Engine.fit_*) against it.
+Engine.fit_*) against it.  The three numpy states here and the three device states of engine.py
+follow one protocol -- update(rows, start), words, like(), merge_words(words), result(...) -- so
+one Accumulator and one combine() serve both.
 
 The optional key "posterior": {"offset": 12.5 | "best", "credible": [0.683, 0.954, 0.997]} adds
 the likelihood-weighted half: a valid row weighs exp(-(chi2 - offset)/2), kept as an integer in
@@ -48,6 +50,7 @@ default 0.025, 0.16, 0.5, 0.84, 0.975) are read from the cumulated weights in ex
 """
 from __future__ import annotations
 
+import ctypes
 import json
 import math
 from dataclasses import dataclass
@@ -414,7 +417,98 @@ def chi2_rows(fit: FitSpec, rows: np.ndarray) -> np.ndarray:
     return c
 
 
-class HostFit:
+def _records(rows) -> np.ndarray:
+    """(n, 6) float64 records of an array or a tensor (a device tensor is read back)."""
+    if hasattr(rows, "detach"):
+        rows = rows.detach().cpu().numpy()
+    return np.asarray(rows, dtype=np.float64).reshape(-1, 6)
+
+
+def _indices(selected) -> np.ndarray:
+    """A selection list (an array or a tensor on any device) as an int64 array."""
+    return np.asarray(selected.cpu() if hasattr(selected, "cpu") else selected, dtype=np.int64).reshape(-1)
+
+
+def check_offset(offset, what: str, optional: bool = False) -> Optional[float]:
+    """The offset of a weighted state as a float: finite and >= 0, or None where the state may be
+    unweighted."""
+    if offset is None and optional:
+        return None
+    offset = float(offset)
+    if not (math.isfinite(offset) and offset >= 0):
+        raise ValueError(f"{what}: the offset must be finite and >= 0, got {offset!r}")
+    return offset
+
+
+def count_rows(state, n: int, what: str) -> None:
+    """state.rows += n, the rows folded into a state of exact sums (merges included): they hold up
+    to POST_MAX_ROWS."""
+    if state.rows + n > POST_MAX_ROWS:
+        raise ValueError(f"{what} state takes at most 2^32 rows (exact 64-bit sums), got {state.rows + n}")
+    state.rows += n
+
+
+# ---- the specs as the C ABI's arrays (include/lzq.h); at least one element each, so none is NULL
+def term_structs(fit: FitSpec):
+    arr = (_native.LzqFitTerm * len(fit.terms))()
+    for k, t in enumerate(fit.terms):
+        arr[k].field, arr[k].target, arr[k].sigma = YIELD_FIELDS.index(t.field), t.target, t.sigma
+    return arr
+
+
+def level_array(fit: FitSpec):
+    return (ctypes.c_double * max(1, len(fit.levels)))(*fit.levels)
+
+
+def map_structs(maps: Sequence[FitMap]):
+    arr = (_native.LzqFitMap * max(1, len(maps)))()
+    for k, m in enumerate(maps):
+        arr[k].n_axes = len(m.axes)
+        for a in range(len(m.axes)):
+            arr[k].stride[a], arr[k].len[a] = m.stride[a], m.len[a]
+    return arr
+
+
+def obs_structs(observables: Sequence["Observable"]):
+    arr = (_native.LzqObs * max(1, len(observables)))()
+    for k, o in enumerate(observables):
+        arr[k].n_axes = len(o.axes)
+        for a, ax in enumerate(o.axes):
+            c = arr[k].axes[a]
+            c.field, c.kind, c.lo, c.hi = YIELD_FIELDS.index(ax.field), int(ax.log), ax.lo, ax.hi
+            c.bins, c.log2_sub = (0, ax.log2_sub) if ax.log else (ax.bins, 0)
+    return arr
+
+
+class _HostState:
+    """What the three numpy states share with each other and with the device states of engine.py:
+    `words` (the state as an int64 tensor, what ranks exchange), like() (an empty state of the same
+    layout and offset), merge_words(words); update(rows, start) and result(...) are each kind's.
+    to_words and load are those of a state kept as its words `w` (HostFit has its own)."""
+    COUNT_WORDS = 0     # the leading words that count the rows of a state of exact sums (count_rows)
+
+    @property
+    def words(self):
+        import torch
+        return torch.from_numpy(self.to_words())
+
+    def merge_words(self, words) -> None:
+        self.merge(self.like().load(words))
+
+    def to_words(self) -> np.ndarray:
+        return self.w.view(np.int64).copy()
+
+    def load(self, words) -> "_HostState":
+        """self.w <- the words of a state of exact sums; its rows are the counts it starts with."""
+        w = np.ascontiguousarray(np.asarray(words), dtype=np.int64).reshape(-1)
+        if w.size != self.w.size:
+            raise ValueError(f"{self.WHAT} state of {w.size} words, expected {self.w.size} for this layout")
+        self.w = w.view(np.uint64).copy()
+        self.rows = int(sum(int(x) for x in self.w[:self.COUNT_WORDS]))
+        return self
+
+
+class HostFit(_HostState):
     """The fit state in numpy: update (rows of flat indices [start, start + n)), merge, result."""
 
     def __init__(self, fit: FitSpec, maps: Sequence[FitMap]):
@@ -432,8 +526,16 @@ class HostFit:
         self.sel = np.empty(0, dtype=np.int64)
         self.sel_total = 0
 
+    def like(self) -> "HostFit":
+        return HostFit(self.fit, self.maps)
+
+    def kept(self):
+        """The selection list (what a rank contributes to the combined one), an int64 tensor."""
+        import torch
+        return torch.from_numpy(self.sel.copy())
+
     def update(self, rows, start: int) -> None:
-        rows = np.asarray(rows, dtype=np.float64).reshape(-1, 6)
+        rows = _records(rows)
         n = rows.shape[0]
         if n == 0:
             return
@@ -518,28 +620,33 @@ class HostFit:
 
     @classmethod
     def from_words(cls, fit: FitSpec, maps: Sequence[FitMap], words, selected=None) -> "HostFit":
-        w = np.ascontiguousarray(np.asarray(words), dtype=np.int64).reshape(-1)
-        if w.size != state_words(maps):
-            raise ValueError(f"fit state of {w.size} words, expected {state_words(maps)} for these maps")
-        s = cls(fit, maps)
-        s.n_valid, s.n_invalid = int(w[W_NVALID]), int(w[W_NINVALID])
-        s.n_within = w[W_WITHIN:W_WITHIN + MAX_LEVELS].copy()
-        s.best_chi2, s.best_idx = w[W_BEST_CHI2:W_BEST_CHI2 + 1].view(np.float64)[0], int(w[W_BEST_IDX])
-        kmin, kmax = w[W_COLMIN:W_COLMIN + 6].view(np.uint64), w[W_COLMAX:W_COLMAX + 6].view(np.uint64)
-        s.col_min = np.where(kmin == _ALL, np.inf, _unkey(np.where(kmin == _ALL, _TOP, kmin)))
-        s.col_max = np.where(kmax == 0, -np.inf, _unkey(np.where(kmax == 0, _TOP, kmax)))
-        s.col_bad = w[W_COLBAD:W_COLBAD + 6].copy()
-        s.sel_total = int(w[W_SEL_TOTAL])
-        off = HEADER_WORDS
-        for k, m in enumerate(maps):
-            s.map_chi2[k] = w[off:off + m.cells].view(np.float64).copy()
-            s.map_idx[k] = w[off + m.cells:off + 2 * m.cells].copy()
-            off += 2 * m.cells
+        s = cls(fit, maps).load(words)
         if selected is not None:
-            s.sel = np.asarray(selected, dtype=np.int64).reshape(-1)
+            s.sel = _indices(selected)
         return s
 
-    def result(self) -> dict:
+    def load(self, words) -> "HostFit":
+        w = np.ascontiguousarray(np.asarray(words), dtype=np.int64).reshape(-1)
+        if w.size != state_words(self.maps):
+            raise ValueError(f"fit state of {w.size} words, expected {state_words(self.maps)} for these maps")
+        self.n_valid, self.n_invalid = int(w[W_NVALID]), int(w[W_NINVALID])
+        self.n_within = w[W_WITHIN:W_WITHIN + MAX_LEVELS].copy()
+        self.best_chi2, self.best_idx = w[W_BEST_CHI2:W_BEST_CHI2 + 1].view(np.float64)[0], int(w[W_BEST_IDX])
+        kmin, kmax = w[W_COLMIN:W_COLMIN + 6].view(np.uint64), w[W_COLMAX:W_COLMAX + 6].view(np.uint64)
+        self.col_min = np.where(kmin == _ALL, np.inf, _unkey(np.where(kmin == _ALL, _TOP, kmin)))
+        self.col_max = np.where(kmax == 0, -np.inf, _unkey(np.where(kmax == 0, _TOP, kmax)))
+        self.col_bad = w[W_COLBAD:W_COLBAD + 6].copy()
+        self.sel_total = int(w[W_SEL_TOTAL])
+        off = HEADER_WORDS
+        for k, m in enumerate(self.maps):
+            self.map_chi2[k] = w[off:off + m.cells].view(np.float64).copy()
+            self.map_idx[k] = w[off + m.cells:off + 2 * m.cells].copy()
+            off += 2 * m.cells
+        return self
+
+    def result(self, selected=None) -> dict:
+        """selected: a selection list assembled elsewhere (the ranks' lists combined), in place of
+        the state's own."""
         cols = {}
         for j, f in enumerate(YIELD_FIELDS):
             any_fin = np.isfinite(self.col_min[j])
@@ -552,7 +659,8 @@ class HostFit:
                          "argmin": self.map_idx[k].reshape(m.len).copy()} for k, m in enumerate(self.maps)],
                "selected": None, "n_selected": None}
         if self.fit.select is not None:
-            res["selected"], res["n_selected"] = self.sel.copy(), int(self.sel_total)
+            res["selected"] = self.sel.copy() if selected is None else _indices(selected)
+            res["n_selected"] = int(self.sel_total)
         return res
 
 
@@ -592,45 +700,68 @@ def post_weights(fit: FitSpec, offset: float, rows) -> np.ndarray:
     """q of (n, 6) float64 records (uint64; Q_INVALID / Q_ABOVE for rows without weight), from the
     library's host build of the one definition (lzq_post_weights_host; no GPU is touched)."""
     rows = np.ascontiguousarray(np.asarray(rows, dtype=np.float64).reshape(-1, 6))
-    terms = (_native.LzqFitTerm * len(fit.terms))()
-    for k, t in enumerate(fit.terms):
-        terms[k].field, terms[k].target, terms[k].sigma = YIELD_FIELDS.index(t.field), t.target, t.sigma
     q = np.empty(rows.shape[0], dtype=np.uint64)
     lib = _native.load()
-    _native.check(lib.lzq_post_weights_host(terms, len(fit.terms), float(offset), rows.ctypes.data, rows.shape[0],
-                                            q.ctypes.data), lib)
+    _native.check(lib.lzq_post_weights_host(term_structs(fit), len(fit.terms), float(offset), rows.ctypes.data,
+                                            rows.shape[0], q.ctypes.data), lib)
     return q
 
 
+# -- sums of weights as (hi, lo) pairs of words, value hi * 2^31 + lo (HostPosterior, HostObservables)
 def _pair(w: np.ndarray, k: int) -> int:
     return (int(w[k]) << 31) + int(w[k + 1])
 
 
-class HostPosterior:
+def _split(q: np.ndarray):
+    """Weights q as the (hi, lo) they add to a pair."""
+    return q >> np.uint64(31), q & np.uint64(0x7FFFFFFF)
+
+
+def _add_pairs(w: np.ndarray, base: int, cell: np.ndarray, hi: np.ndarray, lo: np.ndarray) -> None:
+    """Pair `cell[i]` of the pairs that start at word `base` += (hi[i], lo[i])."""
+    np.add.at(w, base + 2 * cell, hi)
+    np.add.at(w, base + 2 * cell + 1, lo)
+
+
+def _pair_ints(pairs: np.ndarray) -> np.ndarray:
+    """(n, 2) pairs as exact Python integers (an object array)."""
+    return (pairs[:, 0].astype(object) << 31) + pairs[:, 1].astype(object)
+
+
+def _pair_floats(pairs: np.ndarray) -> np.ndarray:
+    """(n, 2) pairs as floats: hi * 2^31 is exact below 2^84, the sum rounds once."""
+    return pairs[:, 0].astype(np.float64) * 2.0 ** 31 + pairs[:, 1].astype(np.float64)
+
+
+def _first_reaching(cum: np.ndarray, p: float) -> int:
+    """The first bin whose cumulated weight `cum` (exact integers, a total > 0) reaches the fraction
+    p of the total: cum * den >= num * total, in integers."""
+    fp = Fraction(p)
+    return int(np.argmax((cum * fp.denominator >= fp.numerator * cum[-1]).astype(bool)))
+
+
+class HostPosterior(_HostState):
     """The posterior state in numpy: `w`, the uint64 words of include/lzq.h's "posterior state".
     update (rows of flat indices [start, start + n)), merge, result."""
+    WHAT, COUNT_WORDS = "a posterior", 4     # the rows a state holds: used, zero, above, invalid
 
     def __init__(self, fit: FitSpec, maps: Sequence[FitMap], offset: float, axis_values: Optional[dict] = None):
-        self.fit, self.maps, self.offset = fit, list(maps), float(offset)
-        if not (math.isfinite(self.offset) and self.offset >= 0):
-            raise ValueError(f"posterior offset must be finite and >= 0, got {offset!r}")
+        self.fit, self.maps, self.offset = fit, list(maps), check_offset(offset, "posterior")
         if any(m.cells > MAX_CELLS for m in self.maps):
             raise ValueError("a fit map has at most 2^24 cells")
         self.axis_values = dict(axis_values or {})
         self.w = np.zeros(post_state_words(self.maps), dtype=np.uint64)
-        self.rows = 0    # rows folded in, merges included: the exact sums hold up to POST_MAX_ROWS
+        self.rows = 0    # rows folded in, merges included (count_rows)
 
-    def _count(self, n: int) -> None:
-        if self.rows + n > POST_MAX_ROWS:
-            raise ValueError(f"a posterior state takes at most 2^32 rows (exact 64-bit sums), got {self.rows + n}")
-        self.rows += n
+    def like(self) -> "HostPosterior":
+        return HostPosterior(self.fit, self.maps, self.offset, self.axis_values)
 
     def update(self, rows, start: int) -> None:
-        rows = np.asarray(rows, dtype=np.float64).reshape(-1, 6)
+        rows = _records(rows)
         n = rows.shape[0]
         if n == 0:
             return
-        self._count(n)
+        count_rows(self, n, self.WHAT)
         q = post_weights(self.fit, self.offset, rows)
         inv, above, zero = q == np.uint64(Q_INVALID), q == np.uint64(Q_ABOVE), q == np.uint64(0)
         used = ~(inv | above | zero)
@@ -639,8 +770,7 @@ class HostPosterior:
             w[k] += np.uint64(int(mask.sum()))
         if not used.any():
             return
-        qu = q[used]
-        hi, lo = qu >> np.uint64(31), qu & np.uint64(0x7FFFFFFF)
+        hi, lo = _split(q[used])
         c = chi2_rows(self.fit, rows)[used]
         idx = np.arange(start, start + n, dtype=np.int64)[used]
 
@@ -650,53 +780,37 @@ class HostPosterior:
         add(PW_Z)
         for l, lev in enumerate(self.fit.levels):
             add(PW_LEVEL + 2 * l, c <= lev)
-        b = np.minimum(POST_BINS - 1, ((c - self.offset) * 16.0).astype(np.int64))
-        np.add.at(w, PW_HIST + 2 * b, hi)
-        np.add.at(w, PW_HIST + 2 * b + 1, lo)
+        _add_pairs(w, PW_HIST, np.minimum(POST_BINS - 1, ((c - self.offset) * 16.0).astype(np.int64)), hi, lo)
         off = PW_MAPS
         for fm in self.maps:
-            cell = fm.cell(idx)
-            np.add.at(w, off + 2 * cell, hi)
-            np.add.at(w, off + 2 * cell + 1, lo)
+            _add_pairs(w, off, fm.cell(idx), hi, lo)
             off += 2 * fm.cells
 
     def merge(self, o: "HostPosterior") -> None:
         """Fold in the state of other (disjoint) rows at the same offset: word-wise addition."""
         if o.offset != self.offset or o.w.size != self.w.size:
             raise ValueError("posterior merge: states of different offsets or layouts")
-        self._count(o.rows)
+        count_rows(self, o.rows, self.WHAT)
         self.w += o.w
-
-    def to_words(self) -> np.ndarray:
-        return self.w.view(np.int64).copy()
 
     @classmethod
     def from_words(cls, fit: FitSpec, maps: Sequence[FitMap], offset: float, words,
                    axis_values: Optional[dict] = None) -> "HostPosterior":
-        w = np.ascontiguousarray(np.asarray(words), dtype=np.int64).reshape(-1)
-        s = cls(fit, maps, offset, axis_values)
-        if w.size != s.w.size:
-            raise ValueError(f"posterior state of {w.size} words, expected {s.w.size} for these maps")
-        s.w = w.view(np.uint64).copy()
-        s.rows = int(sum(int(x) for x in s.w[:4]))
-        return s
+        return cls(fit, maps, offset, axis_values).load(words)
 
-    def result(self) -> dict:
+    def result(self, axis_values: Optional[dict] = None) -> dict:
         """Host values of the state.  Everything is computed from the exact integers in a fixed
         order (integer arithmetic, correctly rounded int / int divisions, math.fsum), so every rank
-        that holds the same words gets the same floats."""
+        that holds the same words gets the same floats.  axis_values: for the state's own."""
+        axis_values = self.axis_values if axis_values is None else axis_values
         w = self.w
         Z = _pair(w, PW_Z)
         hist = w[PW_HIST:PW_MAPS].reshape(POST_BINS, 2).copy()
-        cum, binned, edges = [], 0, []
-        for b in range(POST_BINS):
-            binned += (int(hist[b, 0]) << 31) + int(hist[b, 1])
-            cum.append(binned)
+        cum, edges = np.cumsum(_pair_ints(hist)), []
         for p in self.fit.posterior["credible"] if self.fit.posterior else DEFAULT_CREDIBLE:
             edge = None
-            if binned > 0:
-                fp = Fraction(p)    # exact: the first bin with cum >= p * binned, in integers
-                b = next(b for b in range(POST_BINS) if cum[b] * fp.denominator >= fp.numerator * binned)
+            if cum[-1] > 0:
+                b = _first_reaching(cum, p)
                 edge = None if b == POST_BINS - 1 else (b + 1) / 16.0
             edges.append({"p": p, "delta_chi2": edge})
         res = {"offset": self.offset, "n_used": int(w[PW_NUSED]), "n_zero": int(w[PW_NZERO]),
@@ -708,11 +822,9 @@ class HostPosterior:
         for m in self.maps:
             pairs = w[off:off + 2 * m.cells].reshape(m.cells, 2).copy()
             off += 2 * m.cells
-            # a cell's weight as a float: hi * 2^31 is exact below 2^84, the sum rounds once
-            wf = pairs[:, 0].astype(np.float64) * 2.0 ** 31 + pairs[:, 1].astype(np.float64)
-            post = (wf / np.float64(Z) if Z else np.full(m.cells, np.nan)).reshape(m.len)
+            post = (_pair_floats(pairs) / np.float64(Z) if Z else np.full(m.cells, np.nan)).reshape(m.len)
             mean = std = None
-            x = self.axis_values.get(m.axes[0]) if len(m.axes) == 1 else None
+            x = axis_values.get(m.axes[0]) if len(m.axes) == 1 else None
             if x is not None and Z and len(x) == m.cells:
                 x = [float(v) for v in x]
                 pl = [float(v) for v in post]
@@ -752,18 +864,6 @@ def obs_state_words(observables: Sequence[Observable]) -> int:
     return sum(OBS_HEADER_WORDS + 4 * o.cells for o in observables)
 
 
-def obs_structs(observables: Sequence[Observable]):
-    """The observables as the C ABI's lzq_obs array (at least one element, so it is never NULL)."""
-    arr = (_native.LzqObs * max(1, len(observables)))()
-    for k, o in enumerate(observables):
-        arr[k].n_axes = len(o.axes)
-        for a, ax in enumerate(o.axes):
-            c = arr[k].axes[a]
-            c.field, c.kind, c.lo, c.hi = YIELD_FIELDS.index(ax.field), int(ax.log), ax.lo, ax.hi
-            c.bins, c.log2_sub = (0, ax.log2_sub) if ax.log else (ax.bins, 0)
-    return arr
-
-
 def obs_cells_host(observables: Sequence[Observable], k: int, rows) -> np.ndarray:
     """The classes of (n, 6) records in observable k from the library's host build of the one
     definition (lzq_obs_cells_host; no GPU is touched): what Observable.cell is compared with."""
@@ -775,21 +875,23 @@ def obs_cells_host(observables: Sequence[Observable], k: int, rows) -> np.ndarra
     return out
 
 
-class HostObservables:
+class HostObservables(_HostState):
     """The observable state in numpy: `w`, the uint64 words of include/lzq.h's "sweep observables".
     offset None: unweighted (counts and chi2 minima only); else rows weigh as the posterior's."""
+    WHAT, COUNT_WORDS = "an observable", 3   # the valid rows a state holds: the first one's in, out, non-finite
 
     def __init__(self, fit: FitSpec, observables: Sequence[Observable], offset: Optional[float] = None):
         self.fit, self.observables = fit, list(observables)
-        self.offset = None if offset is None else float(offset)
-        if self.offset is not None and not (math.isfinite(self.offset) and self.offset >= 0):
-            raise ValueError(f"observables: the offset must be finite and >= 0, got {offset!r}")
+        self.offset = check_offset(offset, "observables", optional=True)
         if len(self.observables) > OBS_MAX:
             raise ValueError(f"observables: at most {OBS_MAX}, got {len(self.observables)}")
         self.w = np.zeros(obs_state_words(self.observables), dtype=np.uint64)
         for off, o in self._offsets():
             self.w[off + OBS_HEADER_WORDS + 3 * o.cells:off + OBS_HEADER_WORDS + 4 * o.cells] = _INF_BITS
-        self.rows = 0    # rows folded in, merges included: the exact sums hold up to POST_MAX_ROWS
+        self.rows = 0    # rows folded in, merges included (count_rows)
+
+    def like(self) -> "HostObservables":
+        return HostObservables(self.fit, self.observables, self.offset)
 
     def _offsets(self):
         off = 0
@@ -797,23 +899,19 @@ class HostObservables:
             yield off, o
             off += OBS_HEADER_WORDS + 4 * o.cells
 
-    def _count(self, n: int) -> None:
-        if self.rows + n > POST_MAX_ROWS:
-            raise ValueError(f"an observable state takes at most 2^32 rows (exact 64-bit sums), got {self.rows + n}")
-        self.rows += n
-
-    def update(self, rows) -> None:
-        rows = np.asarray(rows, dtype=np.float64).reshape(-1, 6)
+    def update(self, rows, start: int = 0) -> None:
+        """start: unused (a row's cell does not depend on its index); the states' common signature."""
+        rows = _records(rows)
         n = rows.shape[0]
         if n == 0:
             return
-        self._count(n)
+        count_rows(self, n, self.WHAT)
         c = chi2_rows(self.fit, rows)
         valid = np.isfinite(c)
         if self.offset is not None:
             q = post_weights(self.fit, self.offset, rows)
             has = valid & (q >= np.uint64(1)) & (q <= np.uint64(POST_UNIT))
-            hi, lo = q >> np.uint64(31), q & np.uint64(0x7FFFFFFF)
+            hi, lo = _split(q)
         w = self.w
         for off, o in self._offsets():
             cell = o.cell(rows)
@@ -826,8 +924,7 @@ class HostObservables:
             np.minimum.at(w, base + 3 * o.cells + cell[m], c[m].view(np.uint64))   # chi2 >= 0 orders like its bits
             if self.offset is not None:
                 mw = m & has
-                np.add.at(w, base + 2 * cell[mw], hi[mw])
-                np.add.at(w, base + 2 * cell[mw] + 1, lo[mw])
+                _add_pairs(w, base, cell[mw], hi[mw], lo[mw])
 
     def _chi2_mask(self) -> np.ndarray:
         is_chi2 = np.zeros(self.w.size, dtype=bool)
@@ -839,22 +936,13 @@ class HostObservables:
         """Fold in the state of other (disjoint) rows: words add, the chi2 words take the minimum."""
         if o.offset != self.offset or o.w.size != self.w.size:
             raise ValueError("observables merge: states of different offsets or layouts")
-        self._count(o.rows)
+        count_rows(self, o.rows, self.WHAT)
         self.w = np.where(self._chi2_mask(), np.minimum(self.w, o.w), self.w + o.w)
-
-    def to_words(self) -> np.ndarray:
-        return self.w.view(np.int64).copy()
 
     @classmethod
     def from_words(cls, fit: FitSpec, observables: Sequence[Observable], offset: Optional[float],
                    words) -> "HostObservables":
-        w = np.ascontiguousarray(np.asarray(words), dtype=np.int64).reshape(-1)
-        s = cls(fit, observables, offset)
-        if w.size != s.w.size:
-            raise ValueError(f"observable state of {w.size} words, expected {s.w.size} for these observables")
-        s.w = w.view(np.uint64).copy()
-        s.rows = int(sum(int(x) for x in s.w[:3])) if s.observables else 0   # the valid rows: what the sums hold
-        return s
+        return cls(fit, observables, offset).load(words)
 
     def result(self, z_units: Optional[int] = None) -> List[dict]:
         """Host values of the state, one dictionary an observable.  As HostPosterior.result, everything
@@ -864,11 +952,9 @@ class HostObservables:
         for off, o in self._offsets():
             w, base = self.w, off + OBS_HEADER_WORDS
             pairs = w[base:base + 2 * o.cells].reshape(o.cells, 2).copy()
-            val = (pairs[:, 0].astype(object) << 31) + pairs[:, 1].astype(object)   # exact Python integers
+            val = _pair_ints(pairs)
             total = int(val.sum()) if o.cells else 0
-            # a cell's weight as a float: hi * 2^31 is exact below 2^84, the sum rounds once
-            wf = pairs[:, 0].astype(np.float64) * 2.0 ** 31 + pairs[:, 1].astype(np.float64)
-            post = (wf / np.float64(total) if total else np.full(o.cells, np.nan)).reshape(o.shape)
+            post = (_pair_floats(pairs) / np.float64(total) if total else np.full(o.cells, np.nan)).reshape(o.shape)
             res = {"axes": [a.to_json() for a in o.axes], "edges": [a.edges() for a in o.axes],
                    "weighted": self.offset is not None, "offset": self.offset,
                    "n_in": int(w[off]), "n_out": int(w[off + 1]), "n_nonfinite": int(w[off + 2]),
@@ -884,8 +970,7 @@ class HostObservables:
                 for p in o.quantiles:
                     entry = {"p": p, "bin": None, "lo": None, "hi": None}
                     if total:
-                        fp = Fraction(p)    # exact: the first bin with cum * den >= num * total, in integers
-                        entry.update(span(int(np.argmax((cum * fp.denominator >= fp.numerator * total).astype(bool)))))
+                        entry.update(span(_first_reaching(cum, p)))
                     qs.append(entry)
                 res["quantiles"] = qs
                 if total:
@@ -923,197 +1008,90 @@ def obs_differences(a: Sequence[dict], b: Sequence[dict]) -> List[str]:
     return out
 
 
-# ---- accumulators: what the sweep driver folds chunks into -----------------------------------
-class HostAccumulator:
-    """Chunks of CPU records (the gloo tests, any host table) into a HostFit."""
+# ---- the accumulator: what the sweep driver folds chunks into ---------------------------------
+class Accumulator:
+    """Chunks of records into a fit state `state` and, where the spec asks for them, a posterior
+    state `post` and an observable state `obs`.  engine None: numpy states of CPU records (the gloo
+    tests, any host table); else the engine's device-resident states, updated on the current stream
+    behind the chunk's own kernels.  Nothing else here depends on which."""
 
-    def __init__(self, fit: FitSpec, maps: Sequence[FitMap], axis_values: Optional[dict] = None):
+    def __init__(self, fit: FitSpec, maps: Sequence[FitMap], engine=None, axis_values: Optional[dict] = None):
         self.fit, self.maps, self.axis_values = fit, list(maps), axis_values
-        self.host = HostFit(fit, maps)
+        self._post_state = HostPosterior if engine is None else engine.post_state
+        self._obs_state = HostObservables if engine is None else engine.obs_state
+        self.state = (HostFit if engine is None else engine.fit_state)(fit, self.maps)
         self.post = None    # a numeric posterior offset is folded chunk by chunk; "best" after the combine
         self.obs = None     # observables: unweighted without a posterior, else begun with it
         if fit.posterior is not None and fit.posterior["offset"] != "best":
             self.post_begin(fit.posterior["offset"])
         elif fit.posterior is None and fit.observables:
-            self.obs = HostObservables(fit, fit.observables, None)
+            self.obs = self._obs_state(fit, fit.observables, None)
 
     def update(self, rows, start: int) -> None:
-        rows = rows.detach().numpy() if hasattr(rows, "detach") else rows
-        self.host.update(rows, start)
+        self.state.update(rows, start)    # (with the selection, where the spec has one)
+        self.post_update(rows, start)     # right behind the fit
+
+    def post_begin(self, offset: float) -> None:
+        self.post = self._post_state(self.fit, self.maps, offset)
+        if self.fit.observables:
+            self.obs = self._obs_state(self.fit, self.fit.observables, offset)
+
+    def post_update(self, rows, start: int) -> None:
+        """The states begun so far other than the fit's: the chunk's second half, and the whole of
+        the second pass of the offset "best"."""
         if self.post is not None:
             self.post.update(rows, start)
         if self.obs is not None:
-            self.obs.update(rows)
-
-    def post_begin(self, offset: float) -> None:
-        self.post = HostPosterior(self.fit, self.maps, offset, self.axis_values)
-        if self.fit.observables:
-            self.obs = HostObservables(self.fit, self.fit.observables, offset)
-
-    def post_update(self, rows, start: int) -> None:
-        rows = rows.detach().cpu().numpy() if hasattr(rows, "detach") else rows
-        self.post.update(rows, start)
-        if self.obs is not None:
-            self.obs.update(rows)
-
-    def obs_words(self):
-        import torch
-        return torch.from_numpy(self.obs.to_words())
-
-    def obs_result(self, z_units: Optional[int] = None) -> List[dict]:
-        return self.obs.result(z_units)
-
-    def obs_merged(self, words, z_units: Optional[int] = None) -> List[dict]:
-        """The result of the ranks' observable states `words` [world, n] merged."""
-        import torch
-        tot = HostObservables(self.fit, self.fit.observables, self.obs.offset)
-        for w in torch.as_tensor(words).cpu().numpy():
-            tot.merge(HostObservables.from_words(self.fit, self.fit.observables, self.obs.offset, w))
-        return tot.result(z_units)
-
-    def post_words(self):
-        import torch
-        return torch.from_numpy(self.post.to_words())
-
-    def post_result(self) -> dict:
-        return self.post.result()
-
-    def post_merged(self, words) -> dict:
-        """The result of the ranks' posterior states `words` [world, n] summed."""
-        import torch
-        tot = HostPosterior(self.fit, self.maps, self.post.offset, self.axis_values)
-        for w in torch.as_tensor(words).cpu().numpy():
-            tot.merge(HostPosterior.from_words(self.fit, self.maps, self.post.offset, w))
-        return tot.result()
-
-    def words(self):
-        import torch
-        return torch.from_numpy(self.host.to_words())
-
-    def selected(self):
-        import torch
-        return torch.from_numpy(self.host.sel.copy())
+            self.obs.update(rows, start)
 
     def result(self) -> dict:
-        return self.host.result()
-
-    def merged(self, words, selected) -> dict:
-        """The result of the ranks' states `words` [world, n] merged in rank order."""
-        import torch
-        tot = HostFit(self.fit, self.maps)
-        for w in torch.as_tensor(words).cpu().numpy():
-            tot.merge(HostFit.from_words(self.fit, self.maps, w))
-        if selected is not None:
-            tot.sel = selected.cpu().numpy()
-        return tot.result()
-
-
-class DeviceAccumulator:
-    """Chunks of device records into a device-resident state (lzq_fit_update / lzq_fit_select on the
-    current stream, behind the chunk's own kernels)."""
-
-    def __init__(self, fit: FitSpec, maps: Sequence[FitMap], engine, axis_values: Optional[dict] = None):
-        self.fit, self.maps, self.engine, self.axis_values = fit, list(maps), engine, axis_values
-        self.state = engine.fit_state(fit, maps)
-        self.post = None
-        self.obs = None
-        if fit.posterior is not None and fit.posterior["offset"] != "best":
-            self.post_begin(fit.posterior["offset"])
-        elif fit.posterior is None and fit.observables:
-            self.obs = engine.obs_state(fit, fit.observables, None)
-
-    def update(self, rows, start: int) -> None:
-        self.engine.fit_update(self.state, rows, start)
-        if self.fit.select is not None:
-            self.engine.fit_select(self.state, rows, start)
-        if self.post is not None:   # right behind the fit, on the same stream
-            self.engine.post_update(self.post, rows, start)
-        if self.obs is not None:
-            self.engine.obs_update(self.obs, rows)
-
-    def post_begin(self, offset: float) -> None:
-        self.post = self.engine.post_state(self.fit, self.maps, offset)
-        if self.fit.observables:
-            self.obs = self.engine.obs_state(self.fit, self.fit.observables, offset)
-
-    def post_update(self, rows, start: int) -> None:
-        self.engine.post_update(self.post, rows, start)
-        if self.obs is not None:
-            self.engine.obs_update(self.obs, rows)
-
-    def obs_words(self):
-        return self.obs.words
-
-    def obs_result(self, z_units: Optional[int] = None) -> List[dict]:
-        return self.engine.obs_result(self.obs, z_units)
-
-    def obs_merged(self, words, z_units: Optional[int] = None) -> List[dict]:
-        tot = self.engine.obs_state(self.fit, self.fit.observables, self.obs.offset)
-        for w in words:
-            self.engine.obs_merge(tot, w)
-        return self.engine.obs_result(tot, z_units)
-
-    def post_words(self):
-        return self.post.words
-
-    def post_result(self) -> dict:
-        return self.engine.post_result(self.post, self.axis_values)
-
-    def post_merged(self, words) -> dict:
-        tot = self.engine.post_state(self.fit, self.maps, self.post.offset)
-        for w in words:
-            self.engine.post_merge(tot, w)
-        return self.engine.post_result(tot, self.axis_values)
-
-    def words(self):
-        return self.state.words
-
-    def selected(self):
-        kept = min(int(self.state.words[W_SEL_TOTAL]), self.fit.select[1])
-        return self.state.sel[:kept]
-
-    def result(self) -> dict:
-        return self.engine.fit_result(self.state)
-
-    def merged(self, words, selected) -> dict:
-        tot = self.engine.fit_state(self.fit, self.maps, select=False)
-        for w in words:
-            self.engine.fit_merge(tot, w)
-        return self.engine.fit_result(tot, selected=selected)
+        """The fit of the rows folded in here (combine: of every rank's)."""
+        return self.state.result()
 
 
 def make_accumulator(fit: FitSpec, maps: Sequence[FitMap], engine=None, axis_values: Optional[dict] = None):
     """engine None: records are CPU tensors / arrays (numpy); else the engine's device.
     axis_values (FitSpec.axis_values): the sweep axes' values, for the posterior's means."""
-    if engine is None:
-        return HostAccumulator(fit, maps, axis_values)
-    return DeviceAccumulator(fit, maps, engine, axis_values)
+    return Accumulator(fit, maps, engine, axis_values)
 
 
-def _gather_words(src, world: int, group):
+# ---- combine: the ranks' states gathered and merged ------------------------------------------
+def _distributed() -> bool:
+    import torch.distributed as dist
+    return dist.is_available() and dist.is_initialized()
+
+
+def _gather(src, group):
+    """The ranks' int64 tensors `src` (of one size) as [world, n]; through the CPU unless the group
+    is RCCL's."""
     import torch
     import torch.distributed as dist
+    world = dist.get_world_size(group)
+    src = (src if dist.get_backend(group) == "nccl" else src.cpu()).contiguous()
     flat = torch.empty(world * src.numel(), dtype=torch.int64, device=src.device)   # (gloo takes a flat output)
     dist.all_gather_into_tensor(flat, src, group=group)
     return flat.view(world, src.numel())
 
 
-def combine_posterior(acc, res: dict, local=None, start: int = 0, group=None) -> dict:
-    """The posterior of the whole grid on every rank.  A numeric offset was folded chunk by chunk;
-    "best" is the combined fit's best chi2 (`res`, identical on every rank; 0 when no row is valid)
-    and is applied now, in a second pass over the rank's own shard `local` (rows of flat indices
-    from `start`).  The ranks' states are all-gathered and summed."""
-    import torch.distributed as dist
-    if acc.fit.posterior["offset"] == "best":
-        if local is None:
-            raise ValueError(NO_TABLE_BEST)
-        acc.post_begin(float(res["best"]["chi2"]) if res["best"]["index"] >= 0 else 0.0)
-        acc.post_update(local, start)
-    if not (dist.is_available() and dist.is_initialized()):
-        return acc.post_result()
-    w = acc.post_words()
-    src = (w if dist.get_backend(group) == "nccl" else w.cpu()).contiguous()
-    return acc.post_merged(_gather_words(src, dist.get_world_size(group), group))
+def _merged(state, words):
+    """An empty state like `state` with the ranks' `words` [world, n] merged in rank order."""
+    tot = state.like()
+    for w in words:
+        tot.merge_words(w)
+    return tot
+
+
+def merged_fit(acc, words, selected=None) -> dict:
+    """The fit of the ranks' states `words` [world, n]; selected: their selection lists combined."""
+    return _merged(acc.state, words).result(selected)
+
+
+def merged_posterior(acc, words) -> dict:
+    return _merged(acc.post, words).result(acc.axis_values)
+
+
+def merged_observables(acc, words, z_units: Optional[int] = None) -> List[dict]:
+    return _merged(acc.obs, words).result(z_units)
 
 
 def combine(acc, world: int = 1, group=None, local=None, start: int = 0) -> dict:
@@ -1121,8 +1099,9 @@ def combine(acc, world: int = 1, group=None, local=None, start: int = 0) -> dict
     merged in rank order, their selection lists concatenated in rank order and cut to `cap`
     (shards are contiguous and ascending, so the list stays ascending).  Without a process group
     the rank's own result.  A fit with a "posterior" key gets result["posterior"]
-    (combine_posterior; `local`, `start`: the rank's shard, for the offset "best")."""
-    res = _combine_fit(acc, group)
+    (combine_posterior; `local`, `start`: the rank's shard, for the offset "best").  Every rank
+    issues its collectives in one order: fit words, selection, posterior words, observable words."""
+    res = acc.result() if not _distributed() else merged_fit(acc, *_gather_fit(acc, group))
     if acc.fit.posterior is not None:
         res["posterior"] = combine_posterior(acc, res, local, start, group)
     if acc.fit.observables:
@@ -1130,44 +1109,44 @@ def combine(acc, world: int = 1, group=None, local=None, start: int = 0) -> dict
     return res
 
 
+def _gather_fit(acc, group):
+    """The ranks' fit words [world, n] and, with a selection, their lists combined (else None)."""
+    import torch
+    allw = _gather(acc.state.words, group)
+    if acc.fit.select is None:
+        return allw, None
+    cap = acc.fit.select[1]
+    kept = [min(int(t), cap) for t in allw[:, W_SEL_TOTAL].cpu()]
+    mine = acc.state.kept()
+    pad = torch.zeros(max(kept + [1]), dtype=torch.int64, device=mine.device)   # one size on every rank
+    pad[:mine.numel()] = mine
+    alls = _gather(pad, group)
+    return allw, torch.cat([alls[r, :kept[r]] for r in range(len(kept))])[:cap]
+
+
+def combine_posterior(acc, res: dict, local=None, start: int = 0, group=None) -> dict:
+    """The posterior of the whole grid on every rank.  A numeric offset was folded chunk by chunk;
+    "best" is the combined fit's best chi2 (`res`, identical on every rank; 0 when no row is valid)
+    and is applied now, in a second pass over the rank's own shard `local` (rows of flat indices
+    from `start`).  The ranks' states are all-gathered and summed."""
+    if acc.fit.posterior["offset"] == "best":
+        if local is None:
+            raise ValueError(NO_TABLE_BEST)
+        acc.post_begin(float(res["best"]["chi2"]) if res["best"]["index"] >= 0 else 0.0)
+        acc.post_update(local, start)
+    if not _distributed():
+        return acc.post.result(acc.axis_values)
+    return merged_posterior(acc, _gather(acc.post.words, group))
+
+
 def combine_observables(acc, res: dict, group=None) -> List[dict]:
     """The observables of the whole grid on every rank: the ranks' states (folded behind the fit, or
     with the offset "best" in the posterior's second pass, which combine_posterior has run) are
     all-gathered and merged.  The posterior's Z (`res`) gives each range's share of it."""
-    import torch.distributed as dist
     z = int(res["posterior"]["Z_units"]) if res.get("posterior") is not None else None
-    if not (dist.is_available() and dist.is_initialized()):
-        return acc.obs_result(z)
-    w = acc.obs_words()
-    src = (w if dist.get_backend(group) == "nccl" else w.cpu()).contiguous()
-    return acc.obs_merged(_gather_words(src, dist.get_world_size(group), group), z)
-
-
-def _combine_fit(acc, group=None) -> dict:
-    import torch
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()):
-        return acc.result()
-    world = dist.get_world_size(group)
-    nccl = dist.get_backend(group) == "nccl"
-    w = acc.words()
-    src = (w if nccl else w.cpu()).contiguous()
-    flat = torch.empty(world * src.numel(), dtype=torch.int64, device=src.device)   # (gloo takes a flat output)
-    dist.all_gather_into_tensor(flat, src, group=group)
-    allw = flat.view(world, src.numel())
-    selected = None
-    if acc.fit.select is not None:
-        cap = acc.fit.select[1]
-        kept = [min(int(t), cap) for t in allw[:, W_SEL_TOTAL].cpu()]
-        m = max(kept + [1])
-        mine = acc.selected()
-        pad = torch.zeros(m, dtype=torch.int64, device=src.device)
-        pad[:mine.numel()] = mine.to(src.device)
-        alls = torch.empty(world * m, dtype=torch.int64, device=src.device)
-        dist.all_gather_into_tensor(alls, pad, group=group)
-        alls = alls.view(world, m)
-        selected = torch.cat([alls[r, :kept[r]] for r in range(world)])[:cap]
-    return acc.merged(allw, selected)
+    if not _distributed():
+        return acc.obs.result(z)
+    return merged_observables(acc, _gather(acc.obs.words, group), z)
 
 
 def best_point_yields(compute, best: int, make_out, engine=None) -> Optional[np.ndarray]:

@@ -223,6 +223,75 @@ def test_selection(gpu_engine, tables):
     assert host_result(make_fit(2, select=(-1.0, 100)), [], t, 3)["n_selected"] == 0
 
 
+# ---- one accumulator, two backends -------------------------------------------------------------
+ACC_START, ACC_GRID = 5, (7, 112)       # flat indices 5 .. 781 of a 7 x 112 grid: the last grid row is partial
+ACC_MAPS = [fmap((112, 7), (1, 112)), fmap((1, 112))]
+
+
+def acc_table():
+    """777 quarter-integer rows with two copies of the best row (chi2 0) in different chunks and one
+    row so far out that it weighs nothing at either offset."""
+    t = coarse_table(777, 11)
+    t[[100, 500]] = 0.0
+    t[[100, 500], 0], t[[100, 500], 4] = 1.0, -0.5
+    t[700, 0], t[700, 4] = 1.0, 3.0      # chi2 196: exp(-97) is below 2^-62
+    return t
+
+
+def acc_fit(offset):
+    return F.FitSpec.from_json({
+        "terms": TERMS[:2], "levels": [1.0, 9.0], "select": {"level": 9.0, "cap": 5}, "posterior": {"offset": offset},
+        "observables": [{"axes": [{"field": FIELDS[1], "lo": -1.0, "hi": 1.0, "bins": 16}]},
+                        {"axes": [{"field": FIELDS[2], "lo": 0.3, "hi": 1.2, "per_octave": 4},
+                                  {"field": FIELDS[3], "lo": -2.0, "hi": 1.0, "bins": 6}]}]})
+
+
+def acc_fold(fit, engine, rows, bounds):
+    acc = F.make_accumulator(fit, ACC_MAPS, engine, {"a0": np.linspace(0.0, 1.0, 112)})
+    for a, b in bounds:
+        acc.update(rows[a:b], ACC_START + a)
+    return acc
+
+
+def all_differences(a, b):
+    return (F.differences(a, b) + F.post_differences(a["posterior"], b["posterior"]) +
+            F.obs_differences(a["observables"], b["observables"]))
+
+
+@pytest.mark.parametrize("offset", [2.0, "best"])
+def test_host_and_device_are_one_accumulator(gpu_engine, offset):
+    """The same chunks (300, 300, 177 rows, records on a base that is only 8-byte aligned) through
+    make_accumulator's numpy states and its device states: one combined result, bit for bit, in one
+    pass and as two ranks' words merged by the functions combine() calls behind its gather."""
+    t, fit = acc_table(), acc_fit(offset)
+    buf = torch.empty(t.size + 1, dtype=torch.float64, device=gpu_engine.device)
+    d = buf[1:].view(777, 6)
+    d.copy_(torch.from_numpy(t))
+    assert d.data_ptr() % 16 == 8
+    chunks = ((0, 300), (300, 600), (600, 777))
+    ref = F.combine(acc_fold(fit, None, t, chunks), local=t, start=ACC_START)
+    c = F.chi2_rows(fit, t)
+    post = ref["posterior"]
+    assert ref["n_valid"] > 0 and ref["n_invalid"] > 0 and ref["n_selected"] > 5 == len(ref["selected"])
+    assert (c == np.nanmin(c)).sum() >= 2 and ref["best"]["index"] == ACC_START + int(np.flatnonzero(c == np.nanmin(c))[0])
+    assert post["n_used"] > 0 and (post["n_zero"] > 0 or post["n_above"] > 0)
+    assert all(o["n_in"] > 0 and o["n_out"] > 0 for o in ref["observables"])
+    got = F.combine(acc_fold(fit, gpu_engine, d, chunks), local=d, start=ACC_START)
+    assert all_differences(got, ref) == []
+    for engine, rows in ((None, t), (gpu_engine, d)):
+        parts = [acc_fold(fit, engine, rows, [ab]) for ab in ((0, 400), (400, 777))]
+        for (a, b), acc in zip(((0, 400), (400, 777)), parts):
+            if offset == "best":      # the second pass combine_posterior runs, at the whole table's best chi2
+                acc.post_begin(ref["best"]["chi2"])
+                acc.post_update(rows[a:b], ACC_START + a)
+        stack = lambda get: torch.stack([get(acc) for acc in parts])
+        res = F.merged_fit(parts[0], stack(lambda acc: acc.state.words),
+                           torch.cat([acc.state.kept() for acc in parts])[:5])
+        res["posterior"] = F.merged_posterior(parts[0], stack(lambda acc: acc.post.words))
+        res["observables"] = F.merged_observables(parts[0], stack(lambda acc: acc.obs.words), int(post["Z_units"]))
+        assert all_differences(res, ref) == [], engine
+
+
 # ---- the real engine ---------------------------------------------------------------------------
 def engine_spec():
     sw = pkg("sweep")
