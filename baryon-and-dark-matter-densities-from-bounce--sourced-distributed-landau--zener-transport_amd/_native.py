@@ -63,6 +63,7 @@ FIT_HEADER_WORDS = 32
 POST_HEADER_WORDS, POST_BINS, POST_MAX_ROWS = 32, 2048, 1 << 32  # LZQ_POST_*
 OBS_MAX, OBS_MAX_CELLS, OBS_LDS_CELLS, OBS_HEADER_WORDS = 4, 1 << 20, 1536, 4  # LZQ_OBS_*
 OBS_LINEAR, OBS_LOG2 = 0, 1
+RANK_MAX_N, RANK_HEADER_WORDS = 4096, 8  # LZQ_RANK_*
 
 AOV_FIELDS = ("I_p", "beta_over_H", "T_p_GeV", "v_w", "g_star")
 
@@ -156,7 +157,8 @@ EXPORTS = ("lzq_abi_version", "lzq_last_error", "lzq_init", "lzq_zgrid_init", "l
            "lzq_lz_propagate_profile",
            "lzq_fit_state_bytes", "lzq_fit_reset", "lzq_fit_update", "lzq_fit_select", "lzq_fit_merge",
            "lzq_post_weights_host", "lzq_post_state_bytes", "lzq_post_reset", "lzq_post_update", "lzq_post_merge",
-           "lzq_obs_state_bytes", "lzq_obs_reset", "lzq_obs_update", "lzq_obs_merge", "lzq_obs_cells_host")
+           "lzq_obs_state_bytes", "lzq_obs_reset", "lzq_obs_update", "lzq_obs_merge", "lzq_obs_cells_host",
+           "lzq_rank_state_bytes", "lzq_rank_reset", "lzq_rank_update", "lzq_rank_merge")
 # the lzq_point fields an ODE spline table depends on (A/V kernel fpy:141-156 + window fpy:368-369)
 ODE_TABLE_KEY = ("I_p", "beta_over_H", "T_p_GeV", "v_w", "g_star", "T_min_over_Tp", "T_max_over_Tp")
 # the lzq_point fields the quadrature's z-sums depend on (its y-grid and c; lzq_yields_batch_reuse)
@@ -243,6 +245,10 @@ def load(path: str | None = None):
     L.lzq_obs_update.argtypes = [P(LzqFitTerm), i32, P(LzqObs), i32, i32, d, vp, i64, vp, vp]
     L.lzq_obs_merge.argtypes = [P(LzqObs), i32, vp, vp, vp]
     L.lzq_obs_cells_host.argtypes = [P(LzqObs), i32, i32, vp, i64, vp]
+    L.lzq_rank_state_bytes.argtypes = [i32]
+    L.lzq_rank_reset.argtypes = [i32, vp, vp]
+    L.lzq_rank_update.argtypes = [P(LzqFitTerm), i32, i32, vp, i64, i64, vp, vp]
+    L.lzq_rank_merge.argtypes = [i32, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("lzq_abi_version", "lzq_last_error"):
             getattr(L, name).restype = ctypes.c_int
@@ -250,6 +256,7 @@ def load(path: str | None = None):
     L.lzq_fit_state_bytes.restype = ctypes.c_int64
     L.lzq_post_state_bytes.restype = ctypes.c_int64
     L.lzq_obs_state_bytes.restype = ctypes.c_int64
+    L.lzq_rank_state_bytes.restype = ctypes.c_int64
     if path is None:
         _lib = L
     return L

@@ -259,8 +259,9 @@ class Engine:
         self._keepalive = dev_vals  # axis buffers must outlive the async launch
         return out
 
-    # -- sweep fits, posteriors, observables (lzq_fit_*, lzq_post_*, lzq_obs_*): forwards to the
-    # device-resident states below; fit.py holds the specs and the numpy implementations -------
+    # -- sweep fits, posteriors, observables, ranked points (lzq_fit_*, lzq_post_*, lzq_obs_*,
+    # lzq_rank_*): forwards to the device-resident states below; fit.py holds the specs and the
+    # numpy implementations ---------------------------------------------------------------------
     def fit_state(self, fit, maps, select: bool = True) -> "FitState":
         """An empty device-resident fit state for `fit` (fit.FitSpec) and its resolved maps
         (fit.FitSpec.resolve); select=False leaves out the selection list (a merge target)."""
@@ -327,6 +328,26 @@ class Engine:
         """The observables as host values (fit.HostObservables.result's list): the one
         device-to-host read of the state."""
         return state.result(z_units)
+
+    def rank_state(self, fit, n: int) -> "RankState":
+        """An empty device-resident ranked state for `fit`: the n (1..4096) rows of smallest chi2,
+        in order, each with its flat index and its record."""
+        return RankState(self, fit, n)
+
+    def rank_update(self, state: "RankState", yields: torch.Tensor, start: int) -> None:
+        """Fold the records of flat grid indices [start, start + n), which the state has not seen,
+        into `state`, asynchronously on the current stream."""
+        state.update(yields, start)
+
+    def rank_merge(self, state: "RankState", words: torch.Tensor) -> None:
+        """state <- the n first of state and another state of the same capacity over other rows
+        (its words, from any device)."""
+        state.merge_words(words)
+
+    def rank_result(self, state: "RankState") -> dict:
+        """The ranked points as host values (fit.HostRanked.result's dictionary): the one
+        device-to-host read of the state."""
+        return state.result()
 
     # -- ODE fallback (fpy:200-219, 270-286, 385-417) ---------------------------------------
     def ode_params_to_device(self, recs: np.ndarray) -> torch.Tensor:
@@ -877,6 +898,21 @@ class ObsState(_SweepState):
         y = self._records(yields)
         _fit.count_rows(self, y.shape[0], self.HOST.WHAT)
         self._launch(self._update, *self._head, _vp(y), y.shape[0], _vp(self.words))
+
+
+class RankState(_SweepState):
+    """The ranked points' device-resident state (Engine.rank_state): `words` (include/lzq.h "ranked
+    points") for capacity n."""
+    KIND, HOST = "rank", _fit.HostRanked
+
+    def __init__(self, engine, fit, n: int):
+        self.n = _fit.HostRanked(fit, n).n      # (validates n)
+        super().__init__(engine, (fit, self.n), (self.n,))
+
+    def update(self, yields: torch.Tensor, start: int) -> None:
+        y = self._records(yields)
+        self._launch(self._update, self.c_terms, len(self.fit.terms), self.n, _vp(y), int(start), y.shape[0],
+                     _vp(self.words))
 
 
 class ProfileShapes:

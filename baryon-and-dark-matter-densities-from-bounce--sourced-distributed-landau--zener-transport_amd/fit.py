@@ -47,6 +47,15 @@ in the posterior's second pass), with the same independence of chunking, shardin
 size.  HostObservables is the numpy implementation, written from the definition;
 Engine.obs_* drive the HIP kernel (lzq_obs_update).  "quantiles" (1-D observables with weight;
 default 0.025, 0.16, 0.5, 0.84, 0.975) are read from the cumulated weights in exact integers.
+
+The optional key "ranked": {"n": 1000} (n in 1..4096) keeps the n rows of smallest chi2 themselves,
+in order, each with its flat index and its record: a fourth state (include/lzq.h, "ranked points"),
+folded behind the fit's and independent of the posterior, so it works with --no-table.  Rows are
+ordered by (chi2 bits, flat index) -- a strict total order, since indices are distinct -- so the list
+is one fixed list for every chunking, sharding, world size and merge order.  HostRanked is the numpy
+implementation (a lexsort over the old entries and the chunk); Engine.rank_* drive the HIP kernels
+(lzq_rank_update).  The result goes to fit.json's "ranked" block and to fit_ranked.npz (index, chi2,
+records and params, the sweep axes' values of each point).
 """
 from __future__ import annotations
 
@@ -76,6 +85,8 @@ OBS_MAX, OBS_MAX_CELLS = _native.OBS_MAX, _native.OBS_MAX_CELLS
 OBS_LDS_CELLS, OBS_HEADER_WORDS = _native.OBS_LDS_CELLS, _native.OBS_HEADER_WORDS
 OBS_OUT, OBS_NONFINITE = -1, -2          # lzq_obs_cells_host's classes of a row without a cell
 DEFAULT_QUANTILES = (0.025, 0.16, 0.5, 0.84, 0.975)
+RANK_MAX_N, RANK_HEADER_WORDS = _native.RANK_MAX_N, _native.RANK_HEADER_WORDS
+RW_N, RW_FILLED, RW_NVALID, RW_NINVALID = 0, 1, 2, 3     # word offsets of the ranked state (include/lzq.h)
 NO_TABLE_BEST = ('a posterior with offset "best" takes a second pass over the table, which --no-table does not '
                  'keep: give a number as "offset"')
 # word offsets of the state (include/lzq.h)
@@ -271,8 +282,9 @@ class Observable:
 class FitSpec:
     def __init__(self, terms: Sequence[FitTerm], levels: Sequence[float] = (), maps: Sequence[Sequence[str]] = (),
                  select: Optional[Tuple[float, int]] = None, posterior: Optional[dict] = None,
-                 observables: Optional[Sequence] = None):
+                 observables: Optional[Sequence] = None, ranked: Optional[dict] = None):
         self.posterior = self._posterior(posterior)
+        self.ranked = self._ranked(ranked)
         self.observables = self._observables(observables)
         self.terms = [t if isinstance(t, FitTerm) else FitTerm(*t) for t in terms]
         self.levels = [float(x) for x in levels]
@@ -322,6 +334,18 @@ class FitSpec:
         return {"offset": off, "credible": cred}
 
     @staticmethod
+    def _ranked(r) -> Optional[int]:
+        """{"n": integer in 1..RANK_MAX_N} -> n."""
+        if r is None:
+            return None
+        if not isinstance(r, dict) or set(r) != {"n"}:
+            raise ValueError(f'fit ranked: an object with exactly the key "n", got {r!r}')
+        n = r["n"]
+        if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= RANK_MAX_N:
+            raise ValueError(f"fit ranked: n is an integer in 1..{RANK_MAX_N}, got {n!r}")
+        return int(n)
+
+    @staticmethod
     def _observables(obs) -> List[Observable]:
         if obs is None:
             return []
@@ -333,7 +357,7 @@ class FitSpec:
 
     @classmethod
     def from_json(cls, d: dict) -> "FitSpec":
-        unknown = set(d) - {"terms", "levels", "maps", "select", "posterior", "observables"}
+        unknown = set(d) - {"terms", "levels", "maps", "select", "posterior", "observables", "ranked"}
         if unknown:
             raise ValueError(f"unknown fit-spec keys {sorted(unknown)}")
         try:
@@ -343,7 +367,8 @@ class FitSpec:
             maps = [[m] if isinstance(m, str) else list(m) for m in d.get("maps", [])]
         except (KeyError, TypeError) as e:
             raise ValueError(f"malformed fit spec: {e!r}") from None
-        return cls(terms, d.get("levels", []), maps, select, d.get("posterior"), d.get("observables"))
+        return cls(terms, d.get("levels", []), maps, select, d.get("posterior"), d.get("observables"),
+                   d.get("ranked"))
 
     def to_json(self) -> dict:
         d = {"terms": [{"field": t.field, "target": t.target, "sigma": t.sigma} for t in self.terms],
@@ -354,6 +379,8 @@ class FitSpec:
             d["posterior"] = {"offset": self.posterior["offset"], "credible": list(self.posterior["credible"])}
         if self.observables:
             d["observables"] = [o.to_json() for o in self.observables]
+        if self.ranked is not None:
+            d["ranked"] = {"n": self.ranked}
         return d
 
     def axis_values(self, sweep_spec) -> dict:
@@ -1008,11 +1035,116 @@ def obs_differences(a: Sequence[dict], b: Sequence[dict]) -> List[str]:
     return out
 
 
+# ---- ranked points: the n rows of smallest chi2 with their records ------------------------------
+def rank_state_words(n: int) -> int:
+    return RANK_HEADER_WORDS + 8 * int(n)
+
+
+class HostRanked(_HostState):
+    """The ranked state in numpy: `w`, the uint64 words of include/lzq.h's "ranked points".  The
+    rows seen are ordered by (chi2 bits, flat index); the n first are kept with their records."""
+    WHAT = "a ranked"
+
+    def __init__(self, fit: FitSpec, n: int):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= RANK_MAX_N:
+            raise ValueError(f"ranked: n is an integer in 1..{RANK_MAX_N}, got {n!r}")
+        self.fit, self.n = fit, int(n)
+        self.w = np.zeros(rank_state_words(self.n), dtype=np.uint64)
+        self.w[RW_N] = self.n
+        self._entries()[:] = self._unfilled(self.n)
+        self.rows = 0
+
+    @staticmethod
+    def _unfilled(k: int) -> np.ndarray:
+        e = np.zeros((k, 8), dtype=np.uint64)
+        e[:, 0], e[:, 1] = _INF_BITS, _ALL
+        return e
+
+    def _entries(self) -> np.ndarray:
+        """The n entries as a (n, 8) view of the words."""
+        return self.w[RANK_HEADER_WORDS:].reshape(self.n, 8)
+
+    def like(self) -> "HostRanked":
+        return HostRanked(self.fit, self.n)
+
+    def _take(self, entries: np.ndarray) -> None:
+        """The list <- the n first of its filled entries and `entries` ((k, 8) words of valid rows)."""
+        filled = int(self.w[RW_FILLED])
+        both = np.concatenate([self._entries()[:filled], entries])
+        order = np.lexsort((both[:, 1], both[:, 0]))[:self.n]      # by chi2 bits, then by index
+        self._entries()[:] = np.concatenate([both[order], self._unfilled(self.n - order.size)])
+        self.w[RW_FILLED] = order.size
+
+    def update(self, rows, start: int) -> None:
+        rows = np.ascontiguousarray(_records(rows))
+        n = rows.shape[0]
+        if n == 0:
+            return
+        c = chi2_rows(self.fit, rows)
+        valid = np.isfinite(c)
+        self.w[RW_NVALID] += np.uint64(int(valid.sum()))
+        self.w[RW_NINVALID] += np.uint64(int(n - valid.sum()))
+        e = np.empty((int(valid.sum()), 8), dtype=np.uint64)
+        e[:, 0] = c[valid].view(np.uint64)
+        e[:, 1] = np.arange(start, start + n, dtype=np.int64)[valid].view(np.uint64)
+        e[:, 2:] = rows.view(np.uint64)[valid]
+        self._take(e)
+
+    def merge(self, o: "HostRanked") -> None:
+        """Fold in the state of other (disjoint) rows: the n first of both lists; the counts add."""
+        if o.n != self.n:
+            raise ValueError("ranked merge: states of different capacities")
+        self.w[RW_NVALID] += o.w[RW_NVALID]
+        self.w[RW_NINVALID] += o.w[RW_NINVALID]
+        self._take(o._entries()[:int(o.w[RW_FILLED])])
+
+    @classmethod
+    def from_words(cls, fit: FitSpec, n: int, words) -> "HostRanked":
+        return cls(fit, n).load(words)
+
+    def result(self) -> dict:
+        k = int(self.w[RW_FILLED])
+        e = self._entries()[:k]
+        return {"n": self.n, "count": k, "n_valid": int(self.w[RW_NVALID]), "n_invalid": int(self.w[RW_NINVALID]),
+                "index": e[:, 1].astype(np.int64), "chi2": e[:, 0].copy().view(np.float64),
+                "records": e[:, 2:].copy().view(np.float64)}
+
+
+def rank_differences(a: dict, b: dict) -> List[str]:
+    """Where two ranked results differ (integers exactly, floats by bits); empty when equal."""
+    out = []
+    bits = lambda x: np.ascontiguousarray(x, dtype=np.float64).view(np.int64)
+    for k in ("n", "count", "n_valid", "n_invalid"):
+        if a[k] != b[k]:
+            out.append(f"{k}: {a[k]} != {b[k]}")
+    if a["count"] != b["count"]:
+        return out
+    if not np.array_equal(a["index"], b["index"]):
+        out.append(f"index differs in {int((a['index'] != b['index']).sum())} entries")
+    if not np.array_equal(bits(a["chi2"]), bits(b["chi2"])):
+        out.append(f"chi2 differs in {int((bits(a['chi2']) != bits(b['chi2'])).sum())} entries")
+    if not np.array_equal(bits(a["records"]), bits(b["records"])):
+        out.append(f"records differ in {int((bits(a['records']) != bits(b['records'])).any(axis=1).sum())} entries")
+    return out
+
+
+def ranked_params(sweep_spec, index) -> np.ndarray:
+    """float64[count, n_axes]: the sweep axes' values at each flat index, by the C-order decode
+    (SweepSpec.point_params for every index at once)."""
+    idx = np.asarray(index, dtype=np.int64).reshape(-1).copy()
+    out = np.empty((idx.size, len(sweep_spec.axes)), dtype=np.float64)
+    for a in range(len(sweep_spec.axes) - 1, -1, -1):
+        vals = np.asarray(sweep_spec.axes[a][1], dtype=np.float64)
+        out[:, a] = vals[idx % len(vals)]
+        idx //= len(vals)
+    return out
+
+
 # ---- the accumulator: what the sweep driver folds chunks into ---------------------------------
 class Accumulator:
     """Chunks of records into a fit state `state` and, where the spec asks for them, a posterior
-    state `post` and an observable state `obs`.  engine None: numpy states of CPU records (the gloo
-    tests, any host table); else the engine's device-resident states, updated on the current stream
+    state `post`, an observable state `obs` and a ranked state `rank`.  engine None: numpy states of
+    CPU records (the gloo tests, any host table); else the engine's device-resident states, updated on the current stream
     behind the chunk's own kernels.  Nothing else here depends on which."""
 
     def __init__(self, fit: FitSpec, maps: Sequence[FitMap], engine=None, axis_values: Optional[dict] = None):
@@ -1022,6 +1154,9 @@ class Accumulator:
         self.state = (HostFit if engine is None else engine.fit_state)(fit, self.maps)
         self.post = None    # a numeric posterior offset is folded chunk by chunk; "best" after the combine
         self.obs = None     # observables: unweighted without a posterior, else begun with it
+        self.rank = None    # the n best rows: needs nothing of the posterior
+        if fit.ranked is not None:
+            self.rank = (HostRanked if engine is None else engine.rank_state)(fit, fit.ranked)
         if fit.posterior is not None and fit.posterior["offset"] != "best":
             self.post_begin(fit.posterior["offset"])
         elif fit.posterior is None and fit.observables:
@@ -1029,6 +1164,8 @@ class Accumulator:
 
     def update(self, rows, start: int) -> None:
         self.state.update(rows, start)    # (with the selection, where the spec has one)
+        if self.rank is not None:
+            self.rank.update(rows, start)
         self.post_update(rows, start)     # right behind the fit
 
     def post_begin(self, offset: float) -> None:
@@ -1094,18 +1231,25 @@ def merged_observables(acc, words, z_units: Optional[int] = None) -> List[dict]:
     return _merged(acc.obs, words).result(z_units)
 
 
+def merged_ranked(acc, words) -> dict:
+    return _merged(acc.rank, words).result()
+
+
 def combine(acc, world: int = 1, group=None, local=None, start: int = 0) -> dict:
     """The fit of the whole grid on every rank: the ranks' fixed-size states all-gathered and
     merged in rank order, their selection lists concatenated in rank order and cut to `cap`
     (shards are contiguous and ascending, so the list stays ascending).  Without a process group
     the rank's own result.  A fit with a "posterior" key gets result["posterior"]
     (combine_posterior; `local`, `start`: the rank's shard, for the offset "best").  Every rank
-    issues its collectives in one order: fit words, selection, posterior words, observable words."""
+    issues its collectives in one order: fit words, selection, posterior words, observable words,
+    ranked words.  A fit with a "ranked" key gets result["ranked"] (HostRanked.result)."""
     res = acc.result() if not _distributed() else merged_fit(acc, *_gather_fit(acc, group))
     if acc.fit.posterior is not None:
         res["posterior"] = combine_posterior(acc, res, local, start, group)
     if acc.fit.observables:
         res["observables"] = combine_observables(acc, res, group)
+    if acc.fit.ranked is not None:
+        res["ranked"] = combine_ranked(acc, group)
     return res
 
 
@@ -1149,6 +1293,14 @@ def combine_observables(acc, res: dict, group=None) -> List[dict]:
     return merged_observables(acc, _gather(acc.obs.words, group), z)
 
 
+def combine_ranked(acc, group=None) -> dict:
+    """The n best rows of the whole grid on every rank: the ranks' lists all-gathered and merged in
+    rank order (any order gives the same list)."""
+    if not _distributed():
+        return acc.rank.result()
+    return merged_ranked(acc, _gather(acc.rank.words, group))
+
+
 def best_point_yields(compute, best: int, make_out, engine=None) -> Optional[np.ndarray]:
     """The six yields of grid index `best`, evaluated again through the sweep's own compute function
     (the shard invariant makes them the table's row bit for bit).  The compute function's run
@@ -1170,7 +1322,9 @@ def best_point_yields(compute, best: int, make_out, engine=None) -> Optional[np.
 
 def report(fit: FitSpec, result: dict, sweep_spec, n_points: int, best_yields: Optional[np.ndarray]) -> dict:
     """fit.json / summary.json's "fit" block: the spec, the counts, the column extrema and the best
-    point (index, axis values, yields); the maps and the selection go to their own files."""
+    point (index, axis values, yields); the maps and the selection go to their own files.  With
+    ranked points their axis values are resolved here into result["ranked"]["params"] (write_files
+    saves them: it does not see the sweep)."""
     b = result["best"]
     best = {"chi2": b["chi2"] if b["index"] >= 0 else None, "index": b["index"], "params": None, "final": None}
     if b["index"] >= 0:
@@ -1195,13 +1349,21 @@ def report(fit: FitSpec, result: dict, sweep_spec, n_points: int, best_yields: O
                                "range": [[float(e[0]), float(e[-1])] for e in o["edges"]],   # (log axes: rounded down)
                                "chi2_min": (float(o["chi2_min"].min()) if o["n_in"] else None)}
                               for o in result["observables"]]
+    if result.get("ranked") is not None:
+        r = result["ranked"]
+        r["params"] = ranked_params(sweep_spec, r["index"])
+        rep["ranked"] = {"n": r["n"], "count": r["count"],
+                         "chi2_first": float(r["chi2"][0]) if r["count"] else None,
+                         "chi2_last": float(r["chi2"][-1]) if r["count"] else None,
+                         "axes": [n for n, _ in sweep_spec.axes]}
     return rep
 
 
 def write_files(out_dir: str, rep: dict, result: dict) -> None:
     """fit.json, fit_maps.npz (map<k>_chi2_min / map<k>_argmin; with a posterior map<k>_posterior and
     map<k>_weight, the (cells, 2) uint64 pairs) and selected.npy in `out_dir`; with observables
-    fit_obs.npz (obs<k>_weight, _count, _chi2_min, _posterior and _edges<a> per axis)."""
+    fit_obs.npz (obs<k>_weight, _count, _chi2_min, _posterior and _edges<a> per axis); with ranked
+    points fit_ranked.npz (index, chi2, records, params)."""
     import os
     with open(os.path.join(out_dir, "fit.json"), "w") as f:
         json.dump(rep, f, indent=2)
@@ -1222,3 +1384,7 @@ def write_files(out_dir: str, rep: dict, result: dict) -> None:
             for a, e in enumerate(o["edges"]):
                 arrays[f"obs{k}_edges{a}"] = e
         np.savez(os.path.join(out_dir, "fit_obs.npz"), **arrays)
+    if result.get("ranked") is not None:
+        r = result["ranked"]
+        np.savez(os.path.join(out_dir, "fit_ranked.npz"), index=r["index"], chi2=r["chi2"], records=r["records"],
+                 params=r["params"])

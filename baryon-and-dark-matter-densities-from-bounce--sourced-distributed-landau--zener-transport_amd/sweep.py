@@ -29,7 +29,10 @@ An "observables" key adds histograms over one or two yield fields (lzq_obs_*: pe
 valid rows, the smallest chi2 and, with a posterior, the weight; quantiles and the mode of 1-D ones)
 as an "observables" block of fit.json and a file fit_obs.npz.  They are folded behind the fit --
 unweighted without a posterior, weighted with a numeric offset, both of which work with --no-table --
-or, with the offset "best", in the posterior's second pass.
+or, with the offset "best", in the posterior's second pass.  A "ranked" key ({"n": 1000}, n up to 4096)
+keeps the n points of smallest chi2 themselves, in order, with their records (lzq_rank_*): a "ranked"
+block of fit.json and a file fit_ranked.npz (index, chi2, records, params).  It needs neither a level
+guessed beforehand nor the table, so it works with --no-table.
 
     python -m <package>.sweep --spec C2 --out sweep_c2          # 1 GPU
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m <package>.sweep --spec C4 --out c4
@@ -737,10 +740,11 @@ def main(argv=None):
                     help="nccl (= RCCL over xGMI, default) | gloo (rehearsal: several ranks on one GPU)")
     ap.add_argument("--fit", default=None, metavar="FILE|paper",
                     help="fit the yields to targets on the device, chunk by chunk: a fit-spec JSON (terms, levels, "
-                         "maps, select, posterior, observables; see fit.py), or `paper`: Y_B = 8.72e-11 and DM_over_B = 5.357, "
+                         "maps, select, posterior, observables, ranked; see fit.py), or `paper`: Y_B = 8.72e-11 and DM_over_B = 5.357, "
                          "each with sigma at 1%% of its target (nominal tolerances, not measurement errors).  Writes "
                          "fit.json, fit_maps.npz, selected.npy, with \"observables\" (histograms over yield fields) "
-                         "fit_obs.npz, and a \"fit\" block in summary.json")
+                         "fit_obs.npz, with \"ranked\" (the n best points with their records) fit_ranked.npz, and a "
+                         "\"fit\" block in summary.json")
     ap.add_argument("--no-table", action="store_true",
                     help="with --fit: keep only the fit -- chunks pass through two chunk-sized buffers, there is "
                          "no all-gather, no table.npy and no checkpoint (a grid larger than HBM or the disk)")

@@ -692,6 +692,42 @@ int lzq_obs_merge(const lzq_obs* obs, int32_t n_obs, void* d_dst, const void* d_
 int lzq_obs_cells_host(const lzq_obs* obs, int32_t n_obs, int32_t k, const lzq_yield* rows, int64_t n,
                        int32_t* cell_out);
 
+/* ---- ranked points: the n rows of smallest chi2 with their records -------- */
+/* The fit keeps one best point and lzq_fit_select lists indices within a level in index order; a
+ * RANKED state keeps the n best rows themselves, in order.  The key of a row is (bits of its chi2
+ * as an unsigned 64-bit word, its flat index): chi2 is the fit's expression, a row is valid iff it
+ * is finite, and as a sum of squares it is never negative and never -0, so it orders like its bits.
+ * Row a ranks before row b iff chi2(a) < chi2(b), or they are equal and index(a) < index(b).  Flat
+ * indices are distinct, so this is a strict total order and "the n first rows" is one fixed list
+ * however the rows are cut into chunks, shards or ranks and in whatever order states are merged.
+ *
+ * The state for capacity n (1 .. LZQ_RANK_MAX_N) is LZQ_RANK_HEADER_WORDS + 8 n 64-bit words:
+ *   [0] n  [1] entries filled = min(n, valid rows seen)  [2] valid rows seen  [3] invalid rows seen
+ *   [4..7] reserved, 0 ([4] counts a call's candidates while the call runs on its stream)
+ *   then n entries of 8 words in rank order: chi2 bits, flat index (int64), the six doubles of the
+ *   row's lzq_yield record as bits.  An unfilled entry is (+inf bits, -1, 0, 0, 0, 0, 0, 0).
+ * Two states that saw the same set of rows are equal word for word.  Indices obey
+ * LZQ_FIT_MAX_INDEX; nothing is summed, so there is no limit on the number of rows. */
+#define LZQ_RANK_MAX_N 4096 /* a list's 16-byte keys fit one block's 64 KB of LDS */
+#define LZQ_RANK_HEADER_WORDS 8
+/* Bytes of the state, 8 * (8 + 8 n); negative: an error code (n out of range). */
+int64_t lzq_rank_state_bytes(int32_t n);
+/* The empty state, asynchronously on `stream`. */
+int lzq_rank_reset(int32_t n, void* d_state, void* stream);
+/* Fold records d_yields[count] of flat indices [start, start + count), none of which the state has
+ * seen, into the state.  One streaming pass appends the keys of the rows that rank before the
+ * list's last entry (every valid row while the list is not full) to scratch; one block then sorts
+ * them with the list (a radix select over the 128-bit key first, when there are more than fit its
+ * LDS) and rewrites the list.  A chunk without such a row -- a sweep's steady state -- writes two
+ * counters.  Terms and errors as lzq_fit_update's, plus n outside 1 .. LZQ_RANK_MAX_N; count == 0
+ * is a no-op.  Scratch (16 B a row of the chunk + 64 B an entry) is allocated and freed in stream
+ * order inside the call.  Asynchronous on `stream`, no host synchronisation. */
+int lzq_rank_update(const lzq_fit_term* terms, int32_t n_terms, int32_t n, const lzq_yield* d_yields, int64_t start,
+                    int64_t count, void* d_state, void* stream);
+/* d_dst <- the n first of d_dst and d_src, two states of capacity n over disjoint rows; words [2]
+ * and [3] add. */
+int lzq_rank_merge(int32_t n, void* d_dst, const void* d_src, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
