@@ -17,7 +17,11 @@
 //                               (phi c0..c3, Phi c0..c3), ascending powers of t = xi - xi_j;
 //  * profile_crossings_kernel-- eqs.(5)-(8): every sign change of the cubic Delta on every knot
 //                               interval (split at its stationary points into monotone pieces,
-//                               each root by safeguarded Newton to full precision);
+//                               each root by safeguarded Newton to full precision).  Delta has
+//                               one value per knot (the next row's c0), so a sign flip across a
+//                               junction is a crossing at the knot, a root that only one row's
+//                               rounding shows is not, and the count's parity matches the end signs;
+//                               zeros on the first / last knot are not crossings;
 //  * profile_propagate_kernel-- the time-ordered propagation i dpsi/dt = H psi,
 //                               H = Delta(xi) sigma_z + m_mix(xi) sigma_x, xi = v_w t, through the
 //                               whole profile [xi_0, xi_{K-1}], started in and projected on the
@@ -36,7 +40,8 @@
 //                               (round 5; round 3's per-block staging of whole shapes was 5% slower).
 //                               Large batches launch in (shape, cost, coupling angle) order
 //                               (profile_key_kernel + a radix sort).
-// tests/profile_ref.py restates all three in numpy; tests/test_gpu_profile.py checks them.
+// tests/profile_ref.py restates all three in numpy; tests/test_gpu_profile.py checks them against
+// it, tests/test_gpu_profile_exact.py against exact references (tests/profile_exact.py).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -248,8 +253,12 @@ __global__ __launch_bounds__(kProfBlock) void profile_crossings_kernel(
     pj = -1;
     last = sg;
   };
+  double nD[4];  // the next interval's Delta row, read one interval ahead: its c0 is the knot's value
+  interval_coefs(cf, p, nD, cM);
   for (int j = 0; j + 1 < K; ++j) {
-    interval_coefs(cf + (int64_t)j * kProfCoef, p, cD, cM);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cD[k] = nD[k];
+    if (j + 2 < K) interval_coefs(cf + (int64_t)(j + 1) * kProfCoef, p, nD, cM);
     const double L = x[j + 1] - x[j];
     // monotone pieces: cut at the stationary points of the cubic inside (0, L)
     double cuts[4];
@@ -275,12 +284,27 @@ __global__ __launch_bounds__(kProfBlock) void profile_crossings_kernel(
       if (0.0 < r && r < L) cuts[nc++] = r;
     }
     cuts[nc++] = L;
+    // Delta has ONE value per knot: an interior knot's is the next row's c0 (what the next
+    // interval starts from; this row at t = L agrees with it only to rounding), the last knot's
+    // this row at L.  The walk then sees one sequence of boundary values, so the parity of the
+    // count always matches the signs at the two ends.
+    const double fL = j + 2 < K ? nD[0] : pp0(cD, L);
+    // a piece starts from the value the one before it ended on (the first: c0 = this row at
+    // t = 0, already seen as the previous interval's fL, so only the first knot is met here)
+    double fa = cD[0];
+    if (j == 0) boundary(fa, 0, 0.0);
     for (int k = 0; k + 1 < nc; ++k) {
       const double a = cuts[k], b = cuts[k + 1];
-      const double fa = pp0(cD, a), fb = pp0(cD, b);
-      boundary(fa, j, a);
-      if (fa * fb < 0.0) emit(j, cubic_root(cD, a, b));
+      const bool at_knot = k + 2 == nc;
+      const double fb = at_knot ? fL : pp0(cD, b);
+      if (fa * fb < 0.0) {
+        // a sign change this row's own arithmetic does not show is the jump at the knot itself;
+        // one that only its own arithmetic shows (fa fo < 0 <= fa fb) belongs to no one: skipped
+        const double fo = at_knot ? pp0(cD, b) : fb;
+        emit(j, fa * fo < 0.0 ? cubic_root(cD, a, b) : b);
+      }
       boundary(fb, j, b);
+      fa = fb;  // (of the last piece: unused)
     }
   }
   o_count[i] = cnt;

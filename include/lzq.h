@@ -468,6 +468,10 @@ int lzq_profile_splines(const double* d_knots, const double* d_phi, const double
 
 /* eqs.(5)-(8) per point: every sign change of Delta in [xi_0, xi_{n_knots-1}) (a cubic per knot
  * interval, split at its stationary points; each root by safeguarded Newton to full precision).
+ * Delta has one value per knot (an interior knot's: the next row's c0), so a sign flip across a
+ * knot is one crossing, reported at the knot, and the count's parity matches Delta's signs at the
+ * two ends; a zero exactly on an interior knot, or a whole zero interval, is one crossing (at the
+ * first zero met) iff the signs around it differ; zeros on the first or last knot are none.
  * Up to max_cross crossings per point, in increasing xi, into d_xi / d_dprime (signed Delta'*) /
  * d_m_mix / d_delta_lz [n][max_cross]; d_count[n] = the number found (which may exceed
  * max_cross: the rest are not written; -1 for a bad shape index). */

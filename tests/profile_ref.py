@@ -91,7 +91,12 @@ def crossings(knots, cphi, cPhi, yB, ychi, lam, v_w):
     knot interval's cubic is cut at its stationary points into monotone pieces; a piece whose
     end values have opposite signs holds one root (safeguarded Newton); a zero exactly on a
     piece boundary is a crossing when the last nonzero value before it and the first after it
-    differ in sign (taken where the zero was met)."""
+    differ in sign (taken where the zero was met).  Delta has one value per knot (an interior
+    knot's is the next interval's c0; the previous row evaluated at its length agrees with it only
+    to rounding), so the walk sees one sequence of boundary values: a sign flip across a junction
+    is a crossing at the knot, a root that only one row's rounding shows is not, and the count's
+    parity always matches Delta's signs at the two ends.  Zeros on the first or last knot are not
+    crossings (no sign before / after them)."""
     cD, cM = dm_coefs(cphi, cPhi, yB, ychi, lam)
     out = []
     last = 0.0            # sign of the last nonzero boundary value
@@ -127,11 +132,14 @@ def crossings(knots, cphi, cPhi, yB, ychi, lam, v_w):
             if 0.0 < r < L:
                 cuts.append(r)
         cuts.append(L)
-        for a, b in zip(cuts[:-1], cuts[1:]):
-            fa, fb = pp_eval(c, a), pp_eval(c, b)
+        # one value per knot: an interior knot's is the next row's c0, the last knot's this row at L
+        fL = cD[j + 1][0] if j + 2 < len(knots) else pp_eval(c, L)
+        for k, (a, b) in enumerate(zip(cuts[:-1], cuts[1:])):
+            fa, fo = pp_eval(c, a), pp_eval(c, b)
+            fb = fL if k + 2 == len(cuts) else fo
             last, pend = boundary(fa, j, a, last, pend, emit)
-            if fa * fb < 0.0:
-                emit(j, _root(c, a, b))
+            if fa * fb < 0.0:     # not in this row's own arithmetic: the jump at the knot itself
+                emit(j, _root(c, a, b) if fa * fo < 0.0 else b)
             last, pend = boundary(fb, j, b, last, pend, emit)
     return out
 
