@@ -262,4 +262,51 @@ LZQ_HD double exp2_tab_scaled(double c2N, double g, const double* tabp) {
   return __builtin_fma(Ts, q, Ts);
 }
 
+// ---------------------------------------------------------------------------------------
+// Uniform-entry segments of a z-sum pass (zsum_dispatch in lzq_quad.h calls these; the host
+// test tests/zsum_segments_host.cpp compiles the same source).  g4 is non-decreasing over the
+// grid and starts at >= 0, so t_k = fma(c2N, g4_k, M) moves one way with k, and two stretches of
+// a pass read ONE table entry at every node:
+//   zero:    t at g_max equals M  ->  t_k = M at every node (round(u) = 0: the entry T''[0], the
+//            insert adds 0), with or without the clamp;
+//   clamped: t_k <= M + KMIN      ->  max(t_k, M + KMIN) = M + KMIN from node k on.
+// Both tests evaluate the loop's own expression, so they are exact.  When every lane of a wave
+// passes one, the node's lookup (address, LDS read, exponent insert, and the max) returns the
+// value of the node before: seg_entry fetches it once, seg_node is the rest of the node.
+constexpr double kTabMagic = 0x1.8p52;
+constexpr double kTabTClamp = kTabMagic + (double)kTabKMin;  // exact
+
+// (Mv = kTabMagic here and in seg_node: a parameter so that the device can pin it in a VGPR where
+// it is used, instead of the compiler keeping a copy live across the y-loop)
+LZQ_HD bool seg_zero(double c2N, double g_max, double Mv) { return __builtin_fma(c2N, g_max, Mv) == kTabMagic; }
+LZQ_HD bool seg_clamped(double c2N, double g, double Mv) { return __builtin_fma(c2N, g, Mv) <= kTabTClamp; }
+
+// the scaled table value every node of a segment with the constant (clamped) magic sum tc reads:
+// the general path's address, load and insert, so its bits
+LZQ_HD double seg_entry(const double* tabp, double tc) {
+  const uint32_t k = (uint32_t)__builtin_bit_cast(uint64_t, tc);
+  return tab_scale(tabp[tab_byte_addr(k) >> 3], k);
+}
+
+// one node of a uniform-entry segment (completed-square form): v = Ts * ((r + A)^2 + beta), the
+// operands and operations of exp2_tab_scaled with Ts given.
+LZQ_HD double seg_node(double c2N, double g, double Mv, double Ts) {
+  const double t = __builtin_fma(c2N, g, Mv);
+  const double s = __builtin_fma(c2N, g, (kTabMagic + kSqA) - t);  // the unclamped t, as in the general node
+  return Ts * __builtin_fma(s, s, kSqBeta);
+}
+
+// First node k2 in [0, kend], a multiple of `unroll` (which divides kend), with pred(g4(k2)); pred
+// must be monotone in k (false ... false true ... true); kend if it holds at no batch start.
+template <class Pred, class G4>
+LZQ_HD int seg_first_batch(Pred pred, G4 g4, int kend, int unroll) {
+  int lo = 0, hi = kend / unroll;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (pred(g4(mid * unroll))) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo * unroll;
+}
+
 }  // namespace lzq

@@ -13,7 +13,8 @@
 //     scaled by 2^-512) are read with wave-uniform addresses -> scalar loads into SGPRs, so
 //     every FP64 VALU op of the inner loop takes its table operand from an SGPR;
 //   * the inner exp is the pre-biased 8192-entry LDS table of lzq_exp2.h: 9-10 VALU per
-//     (y, z) node including the accumulate (zsum below);
+//     (y, z) node including the accumulate (zsum in lzq_quad.h), 6 where the whole wave reads
+//     one entry node after node and fetches it once (zsum_uniform);
 //   * per-lane partial sums over its y-nodes are combined by a fixed xor-butterfly, so the
 //     result is a pure function of the point: independent of launch geometry, batch
 //     composition and GPU count (SURVEY §8e bit-identity across W = 1,2,4,8).

@@ -61,6 +61,12 @@ constexpr int kWavesPerBlock = kBlock / kWaveSize;
 #ifndef LZQ_SPLIT_CLAMP
 #define LZQ_SPLIT_CLAMP 0  // clamped passes: the z-nodes no lane can clamp run clamp-free (zsum_dispatch)
 #endif
+// stretches of a pass on which every lane reads ONE table entry at every node (all of a pass whose
+// lanes all have round(u) = 0 or are dead; the all-lanes-clamped tail of a clamped pass) fetch it
+// once and run the node without its lookup (zsum_uniform, zsum_dispatch); 0: every node looks up
+#ifndef LZQ_UNIFORM_SEG
+#define LZQ_UNIFORM_SEG 1
+#endif
 constexpr int kKUnroll = LZQ_KUNROLL;  // z-nodes per scalar-load batch (must divide 1200)
 constexpr int kYB = LZQ_YB;            // y-nodes per lane per pass (independent chains)
 static_assert(kNZ % kKUnroll == 0, "z unroll must divide nz");
@@ -317,6 +323,15 @@ __device__ __forceinline__ double c2_scale() { return EXPV == kExpTable ? (doubl
 //
 // CLAMP = false drops the max (9 VALU/node) on passes whose lanes all satisfy |c2N|*g_max <=
 // N*1534 (no node can leave the clamp range); zsum_dispatch picks it per pass.
+//
+// Where every lane of the wave would read ONE entry at every node -- tc = M on a pass whose lanes
+// all have round(u) = 0 or are dead, tc = M + KMIN from the node at which the last lane clamps --
+// the lookup (address, ds_read, insert, and the max) returns what it returned at the node before.
+// zsum_dispatch finds those stretches per pass with the loop's own t and runs them through
+// zsum_uniform below: the same six FP64 operations per node on the same operands, the entry fetched
+// once (LZQ_UNIFORM_SEG; 80.3% of the C2 workload's nodes, tools/uniform_segment_share.py).  No
+// node is skipped and the bits are the general loop's (tests/test_zsum_segments_host.py,
+// tests/test_gpu_zsum_segments.py).
 template <int YB, int EXPV, bool CLAMP = true>
 __device__ __forceinline__ void zsum(const ZNode* __restrict__ zt, const double* tab, const double (&c2)[YB],
                                      double (&F)[YB], int kend, int kbeg = 0) {
@@ -391,6 +406,35 @@ __device__ __forceinline__ void zsum(const ZNode* __restrict__ zt, const double*
   }
 }
 
+// The uniform-entry loop (LZQ_UNIFORM_SEG): nodes kbeg .. kend of a pass on which every lane's
+// clamped magic sum tc is one constant at every node, so all 64 lanes would fetch the same entry
+// with the same exponent, node after node.  Ts is that entry as the general loop forms it
+// (seg_entry), wave-uniform, an SGPR pair; a node is then exactly the general node's six FP64
+// operations on the same operands in the same order (seg_node: t, w, s, q, v, and F's fma) --
+// no max, no address, no ds_read, no insert.  Every node is executed; F carries on from kbeg in
+// node order like the general loop's.
+template <int YB>
+__device__ __forceinline__ void zsum_uniform(const ZNode* __restrict__ zt, double Ts, const double (&c2)[YB],
+                                             double (&F)[YB], int kend, int kbeg) {
+  if (kbeg == 0) {
+#pragma unroll
+    for (int b = 0; b < YB; ++b) F[b] = 0.0;
+  }
+  const double Mv = vgpr_const(kTabMagic);
+  for (int k = kbeg; k < kend; k += kKUnroll) {
+    double g4[kKUnroll], om[kKUnroll];
+#pragma unroll
+    for (int kk = 0; kk < kKUnroll; ++kk) {
+      g4[kk] = zt[k + kk].g4;
+      om[kk] = zt[k + kk].omega;
+    }
+#pragma unroll
+    for (int kk = 0; kk < kKUnroll; ++kk)
+#pragma unroll
+      for (int b = 0; b < YB; ++b) F[b] = __builtin_fma(om[kk], seg_node(c2[b], g4[kk], Mv, Ts), F[b]);
+  }
+}
+
 // Pass-level wrapper: "dead" lanes, c2 * g4_1 <= -N*1077 (every node k >= 1 underflows to
 // exactly 0: g4 is increasing and omega_0 = 0), run the loop with c2 = 0 and are zeroed
 // afterwards -- the same instruction stream, the exact zero.
@@ -450,7 +494,34 @@ __device__ __forceinline__ void zsum_dispatch(const ZNode* __restrict__ zt, int 
     }
     kend = (lo + kKUnroll - 1) / kKUnroll * kKUnroll;
   }
-  if (EXPV == kExpTable && __all(small)) {
+  if constexpr (EXPV == kExpTable && kSqForm && LZQ_UNIFORM_SEG) {
+    // Uniform-entry segments, decided per pass with the loop's own t = fma(c2, g, M) (lzq_exp2.h):
+    //   every lane has t = M at g_max (small |c2|, or dead: c2e = 0): t = M at every node, the
+    //     whole pass reads T''[0] with nothing inserted;
+    //   else, on a pass that can clamp: from the first batch k2 at whose first node every lane
+    //     has t <= M + KMIN, every lane reads the entry of M + KMIN (t only falls with k); the
+    //     nodes before k2 run the clamped general loop.  A wave-uniform binary search.
+    const double Mv = vgpr_const(kTabMagic);
+    bool zero = true;
+#pragma unroll
+    for (int b = 0; b < YB; ++b) zero = zero && seg_zero(c2e[b], g_max, Mv);
+    if (__all(zero)) {
+      zsum_uniform<YB>(zt, uniform(seg_entry(tab, kTabMagic)), c2e, F, kend, 0);
+    } else if (__all(small)) {
+      zsum<YB, EXPV, false>(zt, tab, c2e, F, kend);
+    } else {
+      const int k2 = seg_first_batch(
+          [&](double g) {
+            bool c = true;
+#pragma unroll
+            for (int b = 0; b < YB; ++b) c = c && seg_clamped(c2e[b], g, Mv);
+            return __all(c) != 0;
+          },
+          [&](int k) { return zt[k].g4; }, kend, kKUnroll);
+      if (k2 > 0) zsum<YB, EXPV, true>(zt, tab, c2e, F, k2);
+      zsum_uniform<YB>(zt, uniform(seg_entry(tab, kTabTClamp)), c2e, F, kend, k2);
+    }
+  } else if (EXPV == kExpTable && __all(small)) {
     zsum<YB, EXPV, false>(zt, tab, c2e, F, kend);
   } else if (EXPV == kExpTable && LZQ_SPLIT_CLAMP) {
     // LZQ_SPLIT_CLAMP: the nodes before the first one at which some lane's u = c2 g4 drops below

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The headline step (bench.py's C2 sweep of 1e6 dense points) for several liblzq.so builds in ONE
-process, interleaved rounds, best of N: tells a box's speed from a library's (box-to-box spread on
+process, interleaved rounds, best of N (every run and each library's max - min beside it): tells a box's speed from a library's (box-to-box spread on
 the same machine code is ~15%, DESIGN.md's numbers table).  Each library's table is compared bit
 for bit with the first one's.
 
@@ -29,7 +29,7 @@ def main():
     engs = {os.path.basename(p): E(0, lib_path=p) for p in a.libs}
     axes = bench.grid_axes(1)
     outs = {k: torch.empty((a.points, 6), dtype=torch.float64, device=e.device) for k, e in engs.items()}
-    best = {}
+    best, runs = {}, {k: [] for k in engs}
     for k, e in engs.items():  # warm-up
         e.sweep(bench.BASE, axes, 0, a.points, out=outs[k])
     torch.cuda.synchronize()
@@ -43,9 +43,11 @@ def main():
             torch.cuda.synchronize()
             ms = t0.elapsed_time(t1)
             best[k] = min(best.get(k, ms), ms)
+            runs[k].append(ms)
     first = next(iter(outs))
     print(json.dumps({"points": a.points, "rounds": a.rounds,
-                      "ms_per_step": best, "points_per_s": {k: a.points / (v / 1e3) for k, v in best.items()},
+                      "ms_per_step": best, "ms_runs": runs,
+                      "spread_ms": {k: max(v) - min(v) for k, v in runs.items()}, "points_per_s": {k: a.points / (v / 1e3) for k, v in best.items()},
                       "bit_identical_to_first": {k: bool(torch.equal(v, outs[first])) for k, v in outs.items()}}))
 
 

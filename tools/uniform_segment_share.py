@@ -1,0 +1,48 @@
+#!/usr/bin/env python3
+"""The share of the headline kernel's (pass, z-node) pairs that run the uniform-entry loop
+(csrc/lzq_quad.h zsum_uniform, LZQ_UNIFORM_SEG) on the C2 workload, counted on the host.
+
+Every C2 point has the same y grid and the same c, so the 125 passes of one point are the whole
+grid.  The passes are planned by tests/zsum_segments_host.cpp, i.e. by the LZQ_HD predicates and
+batch search of csrc/lzq_exp2.h that the device's zsum_dispatch calls (c2 with numpy's exp, <= 1 ulp
+from the device's exp_sc: a pass whose boundary lane sits within 1e-16 of a predicate's threshold
+could be planned differently, by one 8-node batch of 150,000).
+
+    python tools/uniform_segment_share.py
+"""
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import test_zsum_segments_host as H  # noqa: E402
+import zsum_ref as Z                  # noqa: E402
+
+
+def main():
+    B, Tp, I_p = 100.0, 100.0, 0.34                   # yields_config_equal_mass.json (C2's base)
+    y_of = lambda T: 0.5 * B * ((Tp / T) ** 2 - 1.0)
+    ys = np.linspace(max(y_of(5.0 * Tp), -80.0), min(y_of(1e-3 * Tp), 50.0), 8000)
+    g = Z.grid(1200, 30.0)
+    c2 = ((-(I_p / 6.0) * np.exp(np.clip(ys, -50.0, 50.0))) * Z.LOG2E) * 8192.0
+    c2 = np.concatenate([c2, np.full(-len(c2) % 64, c2[-1])])      # tail lanes recompute the last node
+    _, plan = H.run(H.load_lib(), g, c2, 1, 0)
+    path, k2, kend = plan[:, 0], plan[:, 1], plan[:, 2]
+    nodes = int(kend.sum())
+    zero = int(kend[path == H.ZERO].sum())
+    suffix = int((kend - k2)[path == H.SPLIT].sum())
+    split = path == H.SPLIT
+    print(json.dumps({
+        "passes": int(len(path)), "nodes_per_point": nodes,
+        "passes_whole_uniform": int((path == H.ZERO).sum()), "passes_clamp_free": int((path == H.FREE).sum()),
+        "passes_clamped": int(split.sum()), "clamped_passes_with_suffix": int((split & (k2 < kend)).sum()),
+        "k2_of_clamped_passes": k2[split].tolist(),
+        "uniform_nodes_whole_pass": zero, "uniform_nodes_clamped_suffix": suffix,
+        "uniform_share": (zero + suffix) / nodes}))
+
+
+if __name__ == "__main__":
+    main()
