@@ -76,6 +76,25 @@ AOV_DTYPE = np.dtype([(n, "<f8") for n in AOV_FIELDS])
 assert ctypes.sizeof(LzqAovParams) == 40 == AOV_DTYPE.itemsize
 
 
+WINDOW_FIELDS = ("y0", "half_width", "sigma_lo", "sigma_hi", "scale")
+WIN_GAUSS, WIN_PLATEAU, WIN_TABLE = 0, 1, 2  # enum lzq_window_kind
+WINDOW_KINDS = {"gauss": WIN_GAUSS, "plateau": WIN_PLATEAU, "table": WIN_TABLE}
+WIN_MAX_KNOTS, WIN_MAX_TABLES = 4096, 1024  # LZQ_WIN_MAX_*
+
+
+class LzqWindow(ctypes.Structure):  # struct lzq_window: a point's source activity window W(y)
+    _fields_ = [("kind", ctypes.c_int32), ("table", ctypes.c_int32)] + [(n, ctypes.c_double) for n in WINDOW_FIELDS]
+
+
+class LzqWindowTables(ctypes.Structure):  # struct lzq_window_tables (u, W: host or device arrays)
+    _fields_ = [("n_tables", ctypes.c_int32), ("n_knots", ctypes.c_int32), ("u", ctypes.c_void_p),
+                ("W", ctypes.c_void_p)]
+
+
+WINDOW_DTYPE = np.dtype([("kind", "<i4"), ("table", "<i4")] + [(n, "<f8") for n in WINDOW_FIELDS])
+assert ctypes.sizeof(LzqWindow) == 48 == WINDOW_DTYPE.itemsize and ctypes.sizeof(LzqWindowTables) == 24
+
+
 class LzqOdeParams(ctypes.Structure):
     _fields_ = [("sigma_v_chi_GeV_m2", ctypes.c_double), ("Gamma_wash_over_H", ctypes.c_double),
                 ("deplete_DM_from_source", ctypes.c_int32), ("reserved", ctypes.c_int32)]
@@ -152,6 +171,8 @@ EXPORTS = ("lzq_abi_version", "lzq_last_error", "lzq_init", "lzq_zgrid_init", "l
            "lzq_jchi_batch", "lzq_yields_batch", "lzq_sweep_grid", "lzq_sweep_grid_reuse_workspace",
            "lzq_sweep_grid_reuse", "lzq_sweep_grid_ztables", "lzq_sweep_grid_from_ztables",
            "lzq_yields_batch_reuse", "lzq_p_closed_form",
+           "lzq_window_check_host", "lzq_window_eval_host", "lzq_window_batch", "lzq_yields_batch_window",
+           "lzq_yields_batch_reuse_window",
            "lzq_lz_propagate", "lzq_lz_propagate_v", "lzq_ode_tables", "lzq_ode_integrate", "lzq_ode_integrate_shared", "lzq_ode_rows", "lzq_ode_integrate_rows", "lzq_ode_integrate_tp", "lzq_ode_quadrature", "lzq_ode_batch",
            "lzq_ode_aov_T", "lzq_ode_rhs", "lzq_profile_splines", "lzq_profile_crossings",
            "lzq_lz_propagate_profile",
@@ -215,6 +236,12 @@ def load(path: str | None = None):
                                               vp]
     L.lzq_yields_batch_reuse.argtypes = [vp, i64, i32, i32, d, vp, vp, vp, i64, vp, i64, vp, vp]
     L.lzq_p_closed_form.argtypes = [vp, i64, vp, vp]
+    L.lzq_window_check_host.argtypes = [vp, i64, P(LzqWindowTables)]
+    L.lzq_window_eval_host.argtypes = [P(LzqWindow), P(LzqWindowTables), vp, i64, vp, vp]
+    L.lzq_window_batch.argtypes = [P(LzqWindow), P(LzqWindowTables), vp, i64, vp, vp]
+    L.lzq_yields_batch_window.argtypes = [vp, i64, i32, i32, d, vp, vp, vp, vp, P(LzqWindowTables), vp, vp]
+    L.lzq_yields_batch_reuse_window.argtypes = [vp, i64, i32, i32, d, vp, vp, vp, i64, vp, i64, vp,
+                                                P(LzqWindowTables), vp, vp]
     L.lzq_lz_propagate.argtypes = [vp, vp, vp, i64, i32, d, d, i32, vp, vp]
     L.lzq_lz_propagate_v.argtypes = [vp, vp, vp, vp, i64, i32, d, i32, vp, vp]
     L.lzq_ode_tables.argtypes = [vp, i64, vp, vp, i32, i32, d, vp, vp, i64, vp, vp]

@@ -73,6 +73,21 @@ class BoltzmannSystem:
         self.P = float(P_chi_to_B)
         self.m = float(cfg.m_chi_GeV)
         self.aov = AoverVKernel(cfg.I_p, cfg.beta_over_H, cfg.T_p_GeV, cfg.v_w, cfg.g_star)
+        # the source activity window W(y): None = the reference's Gaussian of fpy:262; else a window
+        # block (window.to_window) and, for the table kind, its tables (window.WindowTables or (u, W)).
+        # The quadrature and S_B_T honour it; the ODE operators (build_tables, rhs) raise.
+        self.window = None
+        self.window_tables = None
+
+    def _no_window(self, who: str) -> None:
+        if self.window is not None:
+            raise NotImplementedError(f"{who}: the ODE operators keep the reference's Gaussian window (fpy:226-228); "
+                                      "set bs.window = None")
+
+    def _own_aov(self) -> bool:
+        a, c = self.aov, self.cfg
+        return (a.I_p, a.beta_over_H, a.T_p, a.v_w, a.g_star) == (c.I_p, c.beta_over_H, c.T_p_GeV, max(c.v_w, 1e-12),
+                                                                    c.g_star)
 
     # Cosmology/thermo wrappers (fpy:203-204; scalar host arithmetic, not on the hot path)
     def H(self, T: float) -> float:
@@ -94,12 +109,24 @@ class BoltzmannSystem:
         """fpy:225-228."""
         from .physics_host import y_of_T
         y = y_of_T(T, self.cfg.T_p_GeV, self.cfg.beta_over_H)
-        window = math.exp(-0.5 * (y / max(self.cfg.source_shape_sigma_y, 1e-6)) ** 2)
+        if self.window is not None:
+            from . import window as _window
+            window = float(_window.eval_host(self.window, [y], self.window_tables)[1][0])
+        else:
+            window = math.exp(-0.5 * (y / max(self.cfg.source_shape_sigma_y, 1e-6)) ** 2)
         return self.P * self.J_chi(T) * self.aov.A_over_V_y(y) * window
 
     def integrate_YB_by_quadrature(self, T_lo: float, T_hi: float, n_y: int = 6000) -> float:
         """fpy:231-267 on the GPU (one wavefront)."""
         rec = to_point(self.cfg, P=self.P)
+        if self.window is not None:
+            if not self._own_aov():
+                raise NotImplementedError("integrate_YB_by_quadrature: a window together with a replaced bs.aov's "
+                                          "parameters is not supported (its z grid is)")
+            out = default_engine().yields(rec, n_y=int(n_y), T_lo=[float(T_lo)], T_hi=[float(T_hi)], P=[self.P],
+                                          nz=self.aov.nz, z_max=self.aov.z_max, window=self.window,
+                                          window_tables=self.window_tables)
+            return float(out[0, 0].item())
         out = default_engine().yields(rec, n_y=int(n_y), T_lo=[float(T_lo)], T_hi=[float(T_hi)], P=[self.P],
                                       nz=self.aov.nz, z_max=self.aov.z_max, aov=self.aov)
         return float(out[0, 0].item())
@@ -110,6 +137,7 @@ class BoltzmannSystem:
         not-a-knot cubic spline.  4 <= n <= LZQ_ODE_NT_MAX (scipy's not-a-knot spline needs at
         least 4 knots for the cubic form the library evaluates)."""
         import operator
+        self._no_window("build_tables")
         n = operator.index(n)
         if not 4 <= n <= _native.ODE_NT_MAX:
             raise ValueError(f"build_tables: n = {n} outside [4, {_native.ODE_NT_MAX}]")
@@ -143,6 +171,7 @@ class BoltzmannSystem:
 
     def rhs_batch(self, xs, Ys) -> np.ndarray:
         """Batched fpy:270-286: (n, 2) array of (dY_chi/dx, dY_B/dx)."""
+        self._no_window("rhs")
         self._need_tables()
         return default_engine().ode_rhs(self._rec, to_ode_params(self.cfg), self._T_lo, self._T_hi, self._work, xs,
                                         Ys, nt=self._nt).cpu().numpy()

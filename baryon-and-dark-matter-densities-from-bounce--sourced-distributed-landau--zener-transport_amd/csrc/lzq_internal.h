@@ -34,6 +34,19 @@ int launch_ode_aov_tables_aov(int exp_variant, const lzq_point* d_points, const 
                               int32_t nt, const ZNode* zt, int32_t nzp, const double* gtab, const double* d_T_lo,
                               const double* d_T_hi, double* d_work, int truncate, hipStream_t s, int chunks = 1);
 
+// lzq_window.hip: the quadrature kernels with the window of a per-point lzq_window block, dense and
+// from z-sum tables written by points_ztable_kernel (key_nz, key_z_max: the z grid as a table's
+// header stores it).  window_tables_arg: *d_tables (NULL: none) with its limits checked.
+int window_tables_arg(const lzq_window_tables* d_tables, const char* who, lzq_window_tables& out);
+int launch_yields_points_window(int exp_variant, bool default_grid, const lzq_point* d_points,
+                                const lzq_window* d_win, const lzq_window_tables& wt, int64_t n, int32_t n_y,
+                                const double* d_T_lo, const double* d_T_hi, const double* d_P, const ZNode* zt,
+                                int32_t nzp, const double* gtab, lzq_yield* d_out, int truncate, hipStream_t s);
+int launch_points_reuse_window(const lzq_point* d_points, const lzq_window* d_win, const lzq_window_tables& wt,
+                               int64_t n, int32_t n_y, const double* d_P, double key_nz, double key_z_max,
+                               const int32_t* d_table_index, const double* d_work, int64_t stride, lzq_yield* d_out,
+                               hipStream_t s);
+
 // Longest-first launch order (lzq_propagator.hip): cost bins per point (0 = costliest, kCostBins
 // of them) and their histogram -> offs (kCostBins scratch) and order[n] (a counting sort: one
 // scan, one scatter; stable across bins, atomics order within one).  Sets lzq_last_error.

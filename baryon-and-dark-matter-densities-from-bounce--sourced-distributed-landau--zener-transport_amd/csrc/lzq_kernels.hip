@@ -740,6 +740,27 @@ int lzq_yields_batch(const lzq_point* d_points, int64_t n, int32_t n_y, int32_t 
   return LZQ_OK;
 }
 
+int lzq_yields_batch_window(const lzq_point* d_points, int64_t n, int32_t n_y, int32_t nz, double z_max,
+                            const double* d_T_lo, const double* d_T_hi, const double* d_P, const lzq_window* d_win,
+                            const lzq_window_tables* d_tables, lzq_yield* d_out, void* stream) {
+  if (n < 0 || (n > 0 && (!d_points || !d_out || !d_win)))
+    return fail(LZQ_EINVAL, "lzq_yields_batch_window: bad arguments");
+  if ((d_T_lo == nullptr) != (d_T_hi == nullptr))
+    return fail(LZQ_EINVAL, "lzq_yields_batch_window: T_lo and T_hi must both be given or both be NULL");
+  lzq_window_tables wt;
+  int rc = lzq::window_tables_arg(d_tables, "lzq_yields_batch_window", wt);
+  if (rc) return rc;
+  if (n == 0) return LZQ_OK;
+  int dev;
+  DevZGrid g;
+  rc = zgrid_for(nz, z_max, g, &dev);
+  if (rc) return rc;
+  if (blocks_for(n, lzq::kWavesPerBlock) > kMaxGrid) return fail(LZQ_EINVAL, "lzq_yields_batch_window: n too large");
+  return lzq::launch_yields_points_window(g_exp_variant, g.is_default, d_points, d_win, wt, n, n_y, d_T_lo, d_T_hi,
+                                          d_P, g.zt, g.nzp, exp_table(dev), d_out, g.monotone ? g_truncate : 0,
+                                          (hipStream_t)stream);
+}
+
 namespace {
 // lzq_sweep_grid's argument checks and GridSpec (shared with lzq_sweep_grid_reuse)
 int make_grid(const lzq_point* base, const lzq_axis* axes, int32_t n_axes, int64_t start, int64_t count,
@@ -817,9 +838,12 @@ int lzq_sweep_grid(const lzq_point* base, const lzq_axis* axes, int32_t n_axes, 
   return LZQ_OK;
 }
 
-int lzq_yields_batch_reuse(const lzq_point* d_points, int64_t n, int32_t n_y, int32_t nz, double z_max,
-                           const double* d_P, const int64_t* d_rep, const int32_t* d_table_index, int64_t n_tables,
-                           double* d_work, int64_t work_doubles, lzq_yield* d_out, void* stream) {
+// lzq_yields_batch_reuse, and with d_win lzq_yields_batch_reuse_window (the tables are the same;
+// the integration takes each point's window from its block, lzq_window.hip)
+static int yields_batch_reuse(const lzq_point* d_points, int64_t n, int32_t n_y, int32_t nz, double z_max,
+                              const double* d_P, const int64_t* d_rep, const int32_t* d_table_index, int64_t n_tables,
+                              double* d_work, int64_t work_doubles, const lzq_window* d_win,
+                              const lzq_window_tables* wt, lzq_yield* d_out, void* stream) {
   if (n < 0 || n_tables < 0 || (n > 0 && (!d_points || !d_out || !d_rep || !d_table_index || n_tables == 0)))
     return fail(LZQ_EINVAL, "lzq_yields_batch_reuse: bad arguments");
   const int64_t stride = (n_y > LZQ_NY_MIN ? n_y : LZQ_NY_MIN) + lzq::kTabHdr;
@@ -844,10 +868,32 @@ int lzq_yields_batch_reuse(const lzq_point* d_points, int64_t n, int32_t n_y, in
                        (hipStream_t)stream, d_points, d_rep, n_tables, n_y, stride, g.zt, g.nzp, g.key,
                        exp_table(dev), d_work, trunc);
   LZQ_HIP(hipGetLastError());
+  if (d_win)
+    return lzq::launch_points_reuse_window(d_points, d_win, *wt, n, n_y, d_P, g.key.nz, g.key.z_max, d_table_index,
+                                           d_work, stride, d_out, (hipStream_t)stream);
   hipLaunchKernelGGL(lzq::points_reuse_kernel, dim3((unsigned)nb), dim3(lzq::kBlock), 0, (hipStream_t)stream, d_points,
                      n, n_y, d_P, g.key, d_table_index, d_work, stride, d_out);
   LZQ_HIP(hipGetLastError());
   return LZQ_OK;
+}
+
+int lzq_yields_batch_reuse(const lzq_point* d_points, int64_t n, int32_t n_y, int32_t nz, double z_max,
+                           const double* d_P, const int64_t* d_rep, const int32_t* d_table_index, int64_t n_tables,
+                           double* d_work, int64_t work_doubles, lzq_yield* d_out, void* stream) {
+  return yields_batch_reuse(d_points, n, n_y, nz, z_max, d_P, d_rep, d_table_index, n_tables, d_work, work_doubles,
+                            nullptr, nullptr, d_out, stream);
+}
+
+int lzq_yields_batch_reuse_window(const lzq_point* d_points, int64_t n, int32_t n_y, int32_t nz, double z_max,
+                                  const double* d_P, const int64_t* d_rep, const int32_t* d_table_index,
+                                  int64_t n_tables, double* d_work, int64_t work_doubles, const lzq_window* d_win,
+                                  const lzq_window_tables* d_tables, lzq_yield* d_out, void* stream) {
+  if (n > 0 && !d_win) return fail(LZQ_EINVAL, "lzq_yields_batch_reuse_window: bad arguments");
+  lzq_window_tables wt;
+  const int rc = lzq::window_tables_arg(d_tables, "lzq_yields_batch_reuse_window", wt);
+  if (rc) return rc;
+  return yields_batch_reuse(d_points, n, n_y, nz, z_max, d_P, d_rep, d_table_index, n_tables, d_work, work_doubles,
+                            d_win, &wt, d_out, stream);
 }
 
 int64_t lzq_sweep_grid_reuse_workspace(const lzq_axis* axes, int32_t n_axes, int32_t n_y) {

@@ -230,7 +230,11 @@ __device__ __forceinline__ double rsqrt_pos(double d) {
 // with their reciprocals.  This keeps the per-y work small (the device pow(double) is
 // ~100 VALU and ~40 VGPRs; a division or a sqrt ~10-16) and moves results by ~1e-16 relative
 // (tests: worst golden error unchanged at 1e-13).
-__device__ __forceinline__ YFactors y_factors(const QuadSetup& s, double y, double expy, double wt) {
+//
+// The window W(y) is the caller's: wf(y) is evaluated where the reference's Gaussian proxy stands
+// (gauss_window below, the default); lzq_window.hip passes the window of a point's own block.
+template <typename WinF>
+__device__ __forceinline__ YFactors y_factors(const QuadSetup& s, double y, double expy, double wt, const WinF& wf) {
   YFactors f;
   double T, dTdy, H;
   if (LZQ_YFAST & 2) {
@@ -259,8 +263,7 @@ __device__ __forceinline__ YFactors y_factors(const QuadSetup& s, double y, doub
     vbar = sqrt(pymax(8.0 * T / s.v0, 0.0));
   }
   double J = s.flux * 0.25 * n_eq * vbar;                 // fpy:260
-  double q = (LZQ_YFAST & 4) ? y * s.isig : y / s.sig;
-  f.W = exp_sc(-0.5 * (q * q));                              // fpy:262
+  f.W = wf(y);                                             // fpy:262
   f.PJ = s.P * J;
   f.sHT = sE * H * T;
   f.adTdy = fabs(dTdy);
@@ -269,6 +272,22 @@ __device__ __forceinline__ YFactors y_factors(const QuadSetup& s, double y, doub
   f.live = (y > 50.0) ? 0.0 : 1.0;
   return f;
 }
+
+// fpy:262: the reference's window, exp(-(y/sigma_y)^2 / 2)
+__device__ __forceinline__ double gauss_window(const QuadSetup& s, double y) {
+  double q = (LZQ_YFAST & 4) ? y * s.isig : y / s.sig;
+  return exp_sc(-0.5 * (q * q));
+}
+
+__device__ __forceinline__ YFactors y_factors(const QuadSetup& s, double y, double expy, double wt) {
+  return y_factors(s, y, expy, wt, [&](double yy) { return gauss_window(s, yy); });
+}
+
+// yb_wave's window: W(y) of the point parked in a wave's slot.  The default is the reference's.
+struct SlotGaussWindow {
+  template <typename Slot>
+  static __device__ __forceinline__ double eval(const Slot& slot, double y) { return gauss_window(slot.s, y); }
+};
 
 __device__ __forceinline__ double integrand_from(const YFactors& f, double F) {
   double Av = f.live != 0.0 ? f.pexp * F : 0.0;           // fpy:159-165
@@ -604,10 +623,11 @@ __device__ __forceinline__ int lane_id() {
 // operations in the same lane order in every mode, so Y_B is bit-identical.
 enum YbMode { kYbDense = 0, kYbReuse = 1, kYbTable = 2 };
 
-template <int YB, int EXPV, int MODE = kYbDense, int NZ = 0, typename Slot>
+template <int YB, int EXPV, int MODE = kYbDense, int NZ = 0, typename Win = SlotGaussWindow, typename Slot>
 __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int nzp, const double* tab, int truncate,
                           const double* __restrict__ Fin = nullptr, double* __restrict__ Fout = nullptr) {
   static_assert(MODE == kYbDense || !LZQ_YFACT_EARLY, "table modes re-form the y-factors after the z-loop");
+  static_assert(!LZQ_YFACT_EARLY || __is_same(Win, SlotGaussWindow), "the early y-factors take the default window");
   if (slots[w].s.empty) return 0.0;
   // y-node counts are int32 (n_y of the C ABI): 32-bit loop bounds save the SGPRs that
   // would otherwise spill around the z-loop
@@ -681,7 +701,8 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
 #pragma unroll
     for (int b = 0; b < YB; ++b) {
 #if !LZQ_YFACT_EARLY
-      const YFactors f = y_factors(slots[wr].s, yv[b], ey[b], wt[b]);
+      const YFactors f =
+          y_factors(slots[wr].s, yv[b], ey[b], wt[b], [&](double yy) { return Win::eval(slots[wr], yy); });
 #else
       const YFactors& f = fy[b];
 #endif

@@ -13,7 +13,7 @@ import torch
 
 import logging
 
-from . import _native, fit as _fit
+from . import _native, fit as _fit, window as _window
 from .config import to_aov, to_ctypes_aov, to_ctypes_ode, to_ctypes_point, to_point
 
 _log = logging.getLogger("lzq")
@@ -38,6 +38,7 @@ class Engine:
         self._ztab_key = None  # the grid whose tables _zwork holds (Engine.sweep reuse)
         self._exp_variant = "table"
         self.last_reuse = None
+        self.last_yields_path = None  # the last Engine.yields call: "tables" (z-sums shared) or "dense"
         with torch.cuda.device(self.device):
             self._check(self.lib.lzq_init(self.device.index))
 
@@ -129,6 +130,41 @@ class Engine:
             raise ValueError(f"aov: {rec.size} records for {n} points")
         return _to_device_bytes(rec, self.device)
 
+    def window_tables_to_device(self, tables) -> "DeviceWindowTables":
+        """Tabulated window profiles (window.WindowTables or (u, W), checked on the host by the
+        library) on the device; None: no tables; a DeviceWindowTables passes through."""
+        if isinstance(tables, DeviceWindowTables):
+            return tables
+        return DeviceWindowTables(_window.as_tables(tables), self.device)
+
+    def window_to_device(self, window, n: int, d_tables: "DeviceWindowTables") -> torch.Tensor:
+        """The windows of n points (include/lzq.h lzq_window) as a device byte tensor: one block for
+        every point (a mapping, see window.to_window, or a 1-record WINDOW_DTYPE array) or n records.
+        Host records are checked by the library against d_tables' shape (every refusal of
+        include/lzq.h raises LzqError); a device byte tensor passes as it is (a block the kernels
+        cannot evaluate then gives NaN yields)."""
+        if isinstance(window, torch.Tensor):
+            if window.numel() != n * _native.WINDOW_DTYPE.itemsize:
+                raise ValueError("window: need one lzq_window record per point")
+            return window
+        rec = _window.to_windows(window, n)
+        d_tables.check_blocks(rec)
+        return _to_device_bytes(rec, self.device)
+
+    def window(self, block, ys, tables=None) -> torch.Tensor:
+        """W(y) of one window block at every y on the device (lzq_window_batch): the quadrature
+        kernels' window evaluated alone."""
+        d_wt = self.window_tables_to_device(tables)
+        rec = _window.to_window(block)
+        y = self._f64(ys).reshape(-1)
+        out = torch.empty_like(y)
+        blk = _native.LzqWindow.from_buffer_copy(rec.tobytes())
+        with torch.cuda.device(self.device):
+            self._check(self.lib.lzq_window_batch(ctypes.byref(blk), d_wt.arg, _vp(y), y.numel(), _vp(out),
+                                                  self._stream()))
+        self._keepalive_win = (None, d_wt)
+        return out
+
     # -- fpy:158-165 -----------------------------------------------------------------------
     def aov(self, kernel, ys, nz: int = _native.LZQ_NZ, z_max: float = _native.LZQ_Z_MAX) -> torch.Tensor:
         """A_over_V_y at every y for the kernel AoverVKernel(I_p, beta_over_H, T_p, v_w, g_star, z_max, nz)
@@ -154,7 +190,8 @@ class Engine:
 
     # -- fpy:231-267 + epilogue ----------------------------------------------------------------
     def yields(self, points, n_y: int = 8000, T_lo=None, T_hi=None, P=None, reuse: bool = False,
-               nz: int = _native.LZQ_NZ, z_max: float = _native.LZQ_Z_MAX, aov=None) -> torch.Tensor:
+               nz: int = _native.LZQ_NZ, z_max: float = _native.LZQ_Z_MAX, aov=None, window=None,
+               window_tables=None) -> torch.Tensor:
         """points: POINT_DTYPE numpy array or a device byte tensor from points_to_device.
         Returns (n, 6) float64 device tensor in YIELD_FIELDS order.
         reuse: lzq_yields_batch_reuse -- points equal in _native.ZSUM_KEY share one table of
@@ -162,11 +199,24 @@ class Engine:
         and when points do share; otherwise the dense path.
         nz, z_max: the A/V kernel's z grid (AoverVKernel(..., z_max, nz), fpy:141-156).
         aov: the A/V kernel's own parameters when it is not the points' own (bs.aov replaced,
-        fpy:261; see aov_to_device); such batches run the dense kernels (no reuse)."""
+        fpy:261; see aov_to_device); such batches run the dense kernels (no reuse).
+        window: the source activity window W(y) in place of the Gaussian proxy of fpy:262 (include/lzq.h
+        lzq_window; see window_to_device): one block for all points or n records; the points'
+        source_shape_sigma_y is then not read.  window_tables: the tabulated profiles of the table kind
+        (a window.WindowTables, (u, W), or what window_tables_to_device returned).  The z-sums do not
+        depend on the window, so `reuse` applies as without one.  Not with `aov`."""
         nz, z_max = _native.zgrid(nz, z_max)
         d_pts = points if isinstance(points, torch.Tensor) else self.points_to_device(points)
         n = d_pts.numel() // _native.POINT_DTYPE.itemsize
         d_aov = self.aov_to_device(aov, n)
+        d_win = d_wt = None
+        if window is not None:
+            if d_aov is not None:
+                raise ValueError("yields: a window together with a replaced A/V kernel (aov) is not supported")
+            d_wt = self.window_tables_to_device(window_tables)
+            d_win = self.window_to_device(window, n, d_wt)
+        elif window_tables is not None:
+            raise ValueError("yields: window_tables without a window")
         out = torch.empty((n, 6), dtype=torch.float64, device=self.device)
         tl = None if T_lo is None else self._f64(T_lo)
         th = None if T_hi is None else self._f64(T_hi)
@@ -182,14 +232,27 @@ class Engine:
                     self._zwork = torch.empty(need, dtype=torch.float64, device=self.device)
                 self._ztab_key = None   # the grid tables in _zwork are overwritten
                 idx = inv.to(torch.int32)
-                self._check(self.lib.lzq_yields_batch_reuse(_vp(d_pts), n, int(n_y), nz, z_max, _vp(Pv), _vp(rep),
-                                                              _vp(idx), rep.numel(), _vp(self._zwork),
-                                                              self._zwork.numel(), _vp(out), self._stream()))
-                self._keepalive_reuse = (rep, idx, d_pts)
+                if d_win is not None:
+                    self._check(self.lib.lzq_yields_batch_reuse_window(
+                        _vp(d_pts), n, int(n_y), nz, z_max, _vp(Pv), _vp(rep), _vp(idx), rep.numel(),
+                        _vp(self._zwork), self._zwork.numel(), _vp(d_win), d_wt.arg, _vp(out), self._stream()))
+                else:
+                    self._check(self.lib.lzq_yields_batch_reuse(_vp(d_pts), n, int(n_y), nz, z_max, _vp(Pv), _vp(rep),
+                                                                  _vp(idx), rep.numel(), _vp(self._zwork),
+                                                                  self._zwork.numel(), _vp(out), self._stream()))
+                self._keepalive_reuse = (rep, idx, d_pts, d_win, d_wt)
+                self.last_yields_path = "tables"
+            elif d_win is not None:
+                self._check(self.lib.lzq_yields_batch_window(_vp(d_pts), n, int(n_y), nz, z_max, _vp(tl), _vp(th),
+                                                               _vp(Pv), _vp(d_win), d_wt.arg, _vp(out),
+                                                               self._stream()))
+                self._keepalive_win = (d_win, d_wt)
+                self.last_yields_path = "dense"
             else:
                 self._check(self.lib.lzq_yields_batch(_vp(d_pts), n, int(n_y), nz, z_max, _vp(tl), _vp(th), _vp(Pv),
                                                         _vp(d_aov), _vp(out), self._stream()))
                 self._keepalive_aov = d_aov
+                self.last_yields_path = "dense"
         return out
 
     # -- grid sweep ----------------------------------------------------------------------------
@@ -380,7 +443,7 @@ class Engine:
 
     def ode(self, points, ode_params, max_steps: Optional[int] = None, chunk: int = 1 << 18,
             share_tables: bool = True, method: str = "radau", group_waves: bool = True, nz: int = _native.LZQ_NZ,
-            z_max: float = _native.LZQ_Z_MAX, aov=None, time_parallel: Optional[bool] = None) -> tuple:
+            z_max: float = _native.LZQ_Z_MAX, aov=None, time_parallel: Optional[bool] = None, window=None) -> tuple:
         """fpy:385-417 for n points (POINT_DTYPE records + ODE_DTYPE records, as numpy arrays or
         as device byte tensors from points_to_device / ode_params_to_device): (n, 6) yields
         table and (n,) int32 status (enum lzq_ode_status), both on the device.  Points are
@@ -410,7 +473,12 @@ class Engine:
         through candidate starts) -- the latency path for a few points on long windows, with the
         sequential integration's bits.  None (default): on for a single point (the CLI's case).
         Radau only.  self.last_ode_tp_iters: the Newton updates per point of the last
-        time-parallel call (<= 0: integrated sequentially)."""
+        time-parallel call (<= 0: integrated sequentially).
+        window: must be None -- the ODE path's source term keeps the reference's Gaussian window
+        (include/lzq.h); any other raises."""
+        if window is not None:
+            raise NotImplementedError("Engine.ode takes no window: the ODE entry points integrate the reference's "
+                                      "Gaussian window (fpy:226-228); use Engine.yields(window=...)")
         nz, z_max = _native.zgrid(nz, z_max)
         if method not in ("radau", "quadrature"):
             raise ValueError(f"method must be 'radau' or 'quadrature', got {method!r}")
@@ -913,6 +981,26 @@ class RankState(_SweepState):
         y = self._records(yields)
         self._launch(self._update, self.c_terms, len(self.fit.terms), self.n, _vp(y), int(start), y.shape[0],
                      _vp(self.words))
+
+
+class DeviceWindowTables:
+    """lzq_window_tables with u / W on a device (Engine.window_tables_to_device); `arg` is the
+    pointer the C ABI takes (None without tables)."""
+
+    def __init__(self, host, device):
+        self.n_tables = 0 if host is None else host.n_tables
+        self.n_knots = 0 if host is None else host.n_knots
+        self.arg = None
+        self.host = host
+        if host is not None:
+            self.u = torch.from_numpy(host.u).to(device)
+            self.W = torch.from_numpy(host.W).to(device)
+            self._struct = _native.LzqWindowTables(self.n_tables, self.n_knots, self.u.data_ptr(), self.W.data_ptr())
+            self.arg = ctypes.byref(self._struct)
+
+    def check_blocks(self, rec: np.ndarray) -> None:
+        """lzq_window_check_host for host blocks against these tables."""
+        _window.check(rec, self.host)
 
 
 class ProfileShapes:

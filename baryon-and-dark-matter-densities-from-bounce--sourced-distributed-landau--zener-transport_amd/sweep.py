@@ -116,6 +116,57 @@ class ProfileSpec:
         return X[self.synthetic], A[self.synthetic], B[self.synthetic]
 
 
+# sweep axes over the fields of the spec's window block (include/lzq.h lzq_window)
+WINDOW_AXES = {"window_y0": ("y0",), "window_half_width": ("half_width",), "window_sigma_lo": ("sigma_lo",),
+               "window_sigma_hi": ("sigma_hi",), "window_sigma": ("sigma_lo", "sigma_hi"), "window_scale": ("scale",),
+               "window_table": ("table",)}
+
+
+@dataclass
+class WindowSpec:
+    """The source activity window W(y) of every grid point (PAPER §10 step 4; include/lzq.h
+    lzq_window) in place of the Gaussian proxy of fpy:262: `block` is the base block
+    ({"kind": "gauss" | "plateau" | "table", "y0", "half_width", "sigma_lo", "sigma_hi" | "sigma",
+    "scale", "table"}; window.to_window), which the WINDOW_AXES sweep; u / tables are the tabulated
+    profiles of the table kind (a spec JSON gives them inline, or names a two-column `u,W` file as
+    "csv", which is read once and carried inline from then on, so a checkpoint key follows the
+    file's contents)."""
+    block: dict
+    u: Optional[list] = None
+    tables: Optional[list] = None
+
+    def host_tables(self):
+        from . import window as _window
+        return None if self.u is None else _window.WindowTables(self.u, self.tables)
+
+    def to_json(self) -> dict:
+        d = dict(self.block)
+        if self.u is not None:
+            d["u"], d["tables"] = [float(x) for x in self.u], [[float(x) for x in r] for r in self.tables]
+        return d
+
+    @classmethod
+    def from_json(cls, d: dict) -> "WindowSpec":
+        from . import window as _window
+        d = dict(d)
+        csv, u, tables = d.pop("csv", None), d.pop("u", None), d.pop("tables", None)
+        if csv is not None and (u is not None or tables is not None):
+            raise ValueError("window: give 'csv' or inline 'u' / 'tables', not both")
+        if (u is None) != (tables is None):
+            raise ValueError("window: inline tables need both 'u' (knots) and 'tables' (rows of W)")
+        if csv is not None:
+            t = _window.WindowTables.from_csv(csv)
+        elif u is not None:
+            t = _window.WindowTables(u, tables)
+        else:
+            t = None
+        rec = _window.to_window(d)   # unknown fields / kinds raise here
+        if rec["kind"][0] == _native.WIN_TABLE and t is None:
+            raise ValueError("window: kind 'table' needs 'csv' or inline 'u' / 'tables'")
+        _window.check(rec, t)
+        return cls(d, None if t is None else t.u.tolist(), None if t is None else t.W.tolist())
+
+
 ODE_MAX_STEPS = 1 << 26   # a sweep's default cap on one ODE point's fixed Radau steps (LZQ_ODE_TOO_MANY_STEPS beyond)
 
 
@@ -135,6 +186,7 @@ class SweepSpec:
     # as too_many_steps in summary.json): one long window would otherwise hold its shard for hours.
     # None = no cap (every window the reference accepts, as the single-point CLI does).
     ode_max_steps: Optional[int] = ODE_MAX_STEPS
+    window: Optional[WindowSpec] = None   # None: the reference's window (fpy:262)
 
     @property
     def total(self) -> int:
@@ -164,6 +216,8 @@ class SweepSpec:
             d["nz"], d["z_max"] = int(self.nz), float(self.z_max)
         if self.ode_max_steps != ODE_MAX_STEPS:
             d["ode_max_steps"] = self.ode_max_steps
+        if self.window is not None:
+            d["window"] = self.window.to_json()
         return d
 
     def axis_values(self, start: int, count: int, device) -> dict:
@@ -230,6 +284,8 @@ def grid_records(spec: "SweepSpec", start: int, count: int, engine=None):
             lz[name] = v
         elif name in PROFILE_FIELDS:
             continue          # P comes from the profile (profile_P)
+        elif name in WINDOW_AXES:
+            continue          # a field of the point's window block (window_records)
         elif name in ODE_FIELDS:
             ods[name] = v if name != "deplete_DM_from_source" else (v != 0).astype(np.int32)
         elif name == "Y_chi_init":
@@ -250,6 +306,22 @@ def grid_records(spec: "SweepSpec", start: int, count: int, engine=None):
     return pts, ods
 
 
+def window_records(spec: "SweepSpec", start: int, count: int) -> np.ndarray:
+    """The window blocks (WINDOW_DTYPE) of grid indices [start, start+count): the spec's base block
+    with the WINDOW_AXES values decoded in C order, like grid_records."""
+    from . import window as _window
+    rec = np.repeat(_window.to_window(spec.window.block), count)
+    idx = np.arange(start, start + count, dtype=np.int64)
+    stride = 1
+    for name, vals in reversed(spec.axes):
+        if name in WINDOW_AXES:
+            v = np.asarray(vals, dtype=np.float64)[(idx // stride) % len(vals)]
+            for f in WINDOW_AXES[name]:
+                rec[f] = v.astype(np.int32) if f == "table" else v
+        stride *= len(vals)
+    return rec
+
+
 def _axis_from_json(a: dict) -> Tuple[str, np.ndarray]:
     if "values" in a:
         v = np.asarray(a["values"], dtype=np.float64)
@@ -259,7 +331,8 @@ def _axis_from_json(a: dict) -> Tuple[str, np.ndarray]:
         v = np.linspace(*a["linspace"][:2], int(a["linspace"][2]))
     else:
         raise ValueError(f"axis {a!r} needs values / linspace / logspace")
-    if a["field"] not in _native.FIELD and a["field"] not in ODE_FIELDS and a["field"] not in PROFILE_FIELDS:
+    if a["field"] not in _native.FIELD and a["field"] not in ODE_FIELDS and a["field"] not in PROFILE_FIELDS and \
+            a["field"] not in WINDOW_AXES:
         raise ValueError(f"unknown sweep field {a['field']!r}")
     return a["field"], v
 
@@ -282,13 +355,31 @@ def spec_from_json(d: dict) -> SweepSpec:
         raise ValueError(f"axes {PROFILE_FIELDS} need a 'profile' section")
     if prof is not None and cr is not None:
         raise ValueError("a spec takes either 'crossings' or 'profile'")
+    win = WindowSpec.from_json(d["window"]) if d.get("window") else None
+    for n, v in axes:
+        if n == "window_table" and np.any(v != np.floor(v)):
+            raise ValueError("window_table values must be integers (table indices)")
     nz, z_max = _native.zgrid(d.get("nz", _native.LZQ_NZ), d.get("z_max", _native.LZQ_Z_MAX))
     ms = d.get("ode_max_steps", ODE_MAX_STEPS)
     if ms is not None and int(ms) < 0:
         raise ValueError("ode_max_steps must be >= 0 (0 or null: no cap)")
     # 0 means "no cap", as --ode-max-steps 0 on the command line does (one meaning in both places)
-    return SweepSpec(d.get("name", "custom"), base, axes, int(d.get("n_y", 8000)), d.get("notes", ""), cr, method, prof,
-                     nz, z_max, None if ms is None or int(ms) == 0 else int(ms))
+    spec = SweepSpec(d.get("name", "custom"), base, axes, int(d.get("n_y", 8000)), d.get("notes", ""), cr, method, prof,
+                     nz, z_max, None if ms is None or int(ms) == 0 else int(ms), win)
+    check_window_spec(spec)
+    return spec
+
+
+def check_window_spec(spec: SweepSpec) -> None:
+    """A window on an ODE spec is a usage error: the ODE path keeps the reference's Gaussian
+    (include/lzq.h); window axes need a window."""
+    if spec.window is None:
+        if any(n in WINDOW_AXES for n, _ in spec.axes):
+            raise ValueError(f"axes {tuple(WINDOW_AXES)} need a 'window' section")
+        return
+    if is_ode_spec(spec):
+        raise ValueError("a 'window' section on a spec whose points take the ODE fallback (sigma_v / Gamma_wash / "
+                         "depletion): the ODE path takes no window")
 
 
 def builtin_specs() -> dict:
@@ -670,6 +761,21 @@ def make_compute(spec: SweepSpec, engine, reuse: bool = False) -> ComputeFn:
     without crossings).  reuse: the quadrature's z-sums shared across points with the same
     y-grid and A/V kernel (lzq_sweep_grid_reuse; bit-identical, not the dense headline path)."""
     pcache = {}   # the profile's device splines, built once per sweep
+    check_window_spec(spec)
+    if spec.window is not None:
+        # explicit point records, as the ODE specs', each with its window block; with reuse the
+        # z-sums (which no window enters) are shared by the points equal in _native.ZSUM_KEY
+        d_tables = engine.window_tables_to_device(spec.window.host_tables())
+
+        def compute_window(s, n, out):
+            pts, _ = grid_records(spec, s, n, engine)
+            P_points = coherent_P(spec, s, n, engine) if spec.crossings is not None else None
+            if spec.profile is not None:
+                P_points = profile_P(spec, s, n, engine, pcache)   # the per-point override
+            out.copy_(engine.yields(pts, n_y=spec.n_y, P=P_points, reuse=reuse, nz=spec.nz, z_max=spec.z_max,
+                                    window=window_records(spec, s, n), window_tables=d_tables))
+            engine.last_reuse = engine.last_yields_path
+        return compute_window
     if is_ode_spec(spec):
         counts = np.zeros(8, dtype=np.int64)   # ODE points per lzq_ode_status, this rank (all chunks)
         tables = {"points": 0, "tables": 0, "per_point_chunks": 0, "chunks": 0}   # this run's chunks

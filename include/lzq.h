@@ -251,6 +251,70 @@ int lzq_sweep_grid_from_ztables(const lzq_point* base, const lzq_axis* axes, int
 /* fpy:183-184: P[i] = clamp(1 - exp(-2 pi max(lambda[i], 0)), 0, 1) (naive 1-exp kept). */
 int lzq_p_closed_form(const double* d_lambda, int64_t n, double* d_P, void* stream);
 
+/* ---- source activity window W(y) (fpy:262; PAPER §10 step 4) --------------------------- */
+/* The reference's window is the Gaussian proxy exp(-(y/sigma_y)^2 / 2) of fpy:262, one per-y factor
+ * of the integrand, independent of the z-sums.  The entry points below take the window of each
+ * point from a block of its own instead (csrc/lzq_window.h holds the one definition that the host
+ * and the device build).  In the first two kinds W = exp(-q q / 2), q formed by the IEEE
+ * operations listed, one rounding each:
+ *   LZQ_WIN_GAUSS    q = y r,  r = 1/max(sigma_hi, 1e-6): the operations of the headline kernels;
+ *   LZQ_WIN_PLATEAU  u = y - y0,  d = max(|u| - half_width, 0),  sigma = sigma_lo if u < 0 else
+ *                    sigma_hi,  q = d (1/max(sigma, 1e-6)): a shifted Gaussian, a two-sided one, a
+ *                    flat top with Gaussian shoulders, in the limit a top-hat;
+ *   LZQ_WIN_TABLE    v = (y - y0)/scale,  W = W_k + (v - u_k)((W_{k+1} - W_k)/(u_{k+1} - u_k)) on the
+ *                    knot interval u_k <= v < u_{k+1} (found by binary search), W_0 for v < u_0 and
+ *                    W_last for v >= u_last; no exponential is taken.
+ * A block is refused (LZQ_EINVAL and a message from the host-side checks; NaN yields from a kernel
+ * that meets one in device memory) when any field is NaN, a sigma or the scale is <= 0 or not
+ * finite, half_width < 0, the kind is unknown or, for LZQ_WIN_TABLE, the table index is outside
+ * [0, n_tables).  Every field is checked whatever the kind (neutral values: y0 = 0, half_width = 0,
+ * sigmas = scale = 1, table = 0).  48 bytes. */
+enum lzq_window_kind { LZQ_WIN_GAUSS = 0, LZQ_WIN_PLATEAU = 1, LZQ_WIN_TABLE = 2 };
+typedef struct lzq_window {
+  int32_t kind;  /* enum lzq_window_kind */
+  int32_t table; /* LZQ_WIN_TABLE: row of lzq_window_tables.W */
+  double y0, half_width, sigma_lo, sigma_hi, scale;
+} lzq_window;
+/* Tabulated profiles shared by a batch: n_tables rows W[t][0..n_knots) over one ascending knot
+ * vector u[0..n_knots).  2 <= n_knots <= LZQ_WIN_MAX_KNOTS, 0 <= n_tables <= LZQ_WIN_MAX_TABLES
+ * (0: no table kind in the batch; u and W may then be NULL).  Knots must be finite and strictly
+ * ascending, every W_k finite and >= 0: lzq_window_check_host checks a host copy, which a caller
+ * does before uploading one -- the launches read the device arrays unchecked.  24 bytes. */
+#define LZQ_WIN_MAX_KNOTS 4096
+#define LZQ_WIN_MAX_TABLES 1024
+typedef struct lzq_window_tables {
+  int32_t n_tables, n_knots;
+  const double* u; /* [n_knots] */
+  const double* W; /* [n_tables][n_knots] */
+} lzq_window_tables;
+
+/* Host-side check of n blocks (host array) and of tables whose u / W are HOST arrays (tables may
+ * be NULL when no block is of the table kind): every refusal listed above.  No GPU. */
+int lzq_window_check_host(const lzq_window* win, int64_t n, const lzq_window_tables* host_tables);
+/* The host build of the window: for one block and n host values of y, q_or_v[i] = q (the v of a
+ * table kind) and W[i] with libm's exp (the interpolated W of a table kind); either output may be
+ * NULL.  host_tables as for lzq_window_check_host, whose checks run first.  No GPU. */
+int lzq_window_eval_host(const lzq_window* win, const lzq_window_tables* host_tables, const double* y, int64_t n,
+                         double* q_or_v, double* W);
+/* The device build: d_W[i] = W(d_y[i]) for one host-side block; d_tables' u / W are device arrays
+ * (NULL for the other kinds).  The exponential is the quadrature kernels' (<= 1 ulp). */
+int lzq_window_batch(const lzq_window* win, const lzq_window_tables* d_tables, const double* d_y, int64_t n,
+                     double* d_W, void* stream);
+/* lzq_yields_batch (without an A/V block) with point i's window taken from d_win[i] (device
+ * array) instead of its source_shape_sigma_y, which is then not read.  A LZQ_WIN_GAUSS block whose
+ * sigma_hi is the point's source_shape_sigma_y gives lzq_yields_batch's bits. */
+int lzq_yields_batch_window(const lzq_point* d_points, int64_t n, int32_t n_y, int32_t nz, double z_max,
+                            const double* d_T_lo, const double* d_T_hi, const double* d_P, const lzq_window* d_win,
+                            const lzq_window_tables* d_tables, lzq_yield* d_out, void* stream);
+/* lzq_yields_batch_reuse likewise: the z-sum tables do not depend on the window, so points that
+ * differ only in their windows share one.  Bit-identical to lzq_yields_batch_window. */
+int lzq_yields_batch_reuse_window(const lzq_point* d_points, int64_t n, int32_t n_y, int32_t nz, double z_max,
+                                  const double* d_P, const int64_t* d_rep, const int32_t* d_table_index,
+                                  int64_t n_tables, double* d_work, int64_t work_doubles, const lzq_window* d_win,
+                                  const lzq_window_tables* d_tables, lzq_yield* d_out, void* stream);
+/* The ODE entry points below take no window: their source term keeps the reference's Gaussian
+ * (fpy:226-228).  Engine.ode and the facade's ODE operators raise when given another one. */
+
 /* ---- ODE fallback (fpy:200-219, 270-286, 385-417) -------------------------------------- */
 /* Configurations with sigma_v != 0, Gamma_wash != 0 or depletion leave the fast path
  * (fpy:372) for the reference's Boltzmann ODE.  These three Config fields ride next to the
