@@ -125,6 +125,10 @@ assert ctypes.sizeof(LzqYield) == 48
 # enum lzq_field
 FIELD = {n: i for i, n in enumerate(POINT_DOUBLE_FIELDS)}
 FIELD.update({"delta_LZ": 32, "m_mix": 33, "dprime": 34})
+# LZQ_F_WIN_*: the axes over the fields of a point's window block (sweep.WINDOW_AXES), accepted by the
+# *_window grid entry points only
+WINDOW_FIELD = {"window_y0": 64, "window_half_width": 65, "window_sigma_lo": 66, "window_sigma_hi": 67,
+                "window_sigma": 68, "window_scale": 69, "window_table": 70}
 FERMION, BOSON = 0, 1
 THERMAL, NONTHERMAL, REGIME_OTHER = 0, 1, 2
 LZQ_NZ, LZQ_Z_MAX = 1200, 30.0  # fpy:142 AoverVKernel defaults, main()'s grid (fpy:197)
@@ -173,6 +177,8 @@ EXPORTS = ("lzq_abi_version", "lzq_last_error", "lzq_init", "lzq_zgrid_init", "l
            "lzq_yields_batch_reuse", "lzq_p_closed_form",
            "lzq_window_check_host", "lzq_window_eval_host", "lzq_window_batch", "lzq_yields_batch_window",
            "lzq_yields_batch_reuse_window",
+           "lzq_sweep_grid_window", "lzq_sweep_grid_reuse_window", "lzq_sweep_grid_ztables_window",
+           "lzq_sweep_grid_from_ztables_window", "lzq_window_grid_blocks_host", "lzq_window_grid_check_host",
            "lzq_lz_propagate", "lzq_lz_propagate_v", "lzq_ode_tables", "lzq_ode_integrate", "lzq_ode_integrate_shared", "lzq_ode_rows", "lzq_ode_integrate_rows", "lzq_ode_integrate_tp", "lzq_ode_quadrature", "lzq_ode_batch",
            "lzq_ode_aov_T", "lzq_ode_rhs", "lzq_profile_splines", "lzq_profile_crossings",
            "lzq_lz_propagate_profile",
@@ -242,6 +248,15 @@ def load(path: str | None = None):
     L.lzq_yields_batch_window.argtypes = [vp, i64, i32, i32, d, vp, vp, vp, vp, P(LzqWindowTables), vp, vp]
     L.lzq_yields_batch_reuse_window.argtypes = [vp, i64, i32, i32, d, vp, vp, vp, i64, vp, i64, vp,
                                                 P(LzqWindowTables), vp, vp]
+    L.lzq_sweep_grid_window.argtypes = [P(LzqPoint), P(LzqWindow), P(LzqAxis), i32, i64, i64, i32, i32, d, vp,
+                                        P(LzqWindowTables), vp, vp]
+    L.lzq_sweep_grid_reuse_window.argtypes = [P(LzqPoint), P(LzqWindow), P(LzqAxis), i32, i64, i64, i32, i32, d, vp,
+                                              vp, i64, P(LzqWindowTables), vp, vp]
+    L.lzq_sweep_grid_ztables_window.argtypes = [P(LzqPoint), P(LzqAxis), i32, i32, i32, d, vp, i64, vp]
+    L.lzq_sweep_grid_from_ztables_window.argtypes = [P(LzqPoint), P(LzqWindow), P(LzqAxis), i32, i64, i64, i32, i32,
+                                                     d, vp, vp, i64, P(LzqWindowTables), vp, vp]
+    L.lzq_window_grid_blocks_host.argtypes = [P(LzqWindow), P(LzqAxis), i32, i64, i64, vp]
+    L.lzq_window_grid_check_host.argtypes = [P(LzqWindow), P(LzqAxis), i32, P(LzqWindowTables)]
     L.lzq_lz_propagate.argtypes = [vp, vp, vp, i64, i32, d, d, i32, vp, vp]
     L.lzq_lz_propagate_v.argtypes = [vp, vp, vp, vp, i64, i32, d, i32, vp, vp]
     L.lzq_ode_tables.argtypes = [vp, i64, vp, vp, i32, i32, d, vp, vp, i64, vp, vp]

@@ -47,6 +47,21 @@ int launch_points_reuse_window(const lzq_point* d_points, const lzq_window* d_wi
                                const int32_t* d_table_index, const double* d_work, int64_t stride, lzq_yield* d_out,
                                hipStream_t s);
 
+// The grid forms (lzq_sweep_grid_window, lzq_sweep_grid_from_ztables_window): point, block and table
+// index decoded from the flat index in the kernel; grid: make_grid's GridSpec (lzq_kernels.hip), with
+// tstride set for the reuse kernel.  window_axes_check: LZQ_EINVAL when two axes write the same
+// field of the window block.
+struct GridSpec;  // lzq_quad.h
+int window_axes_check(const lzq_axis* axes, int32_t n_axes, const char* who);
+int launch_yields_grid_window(int exp_variant, bool default_grid, const lzq_point& base, const lzq_window& base_win,
+                              const GridSpec& grid, const lzq_window_tables& wt, int64_t start, int64_t count,
+                              int32_t n_y, const double* d_P, const ZNode* zt, int32_t nzp, const double* gtab,
+                              lzq_yield* d_out, int truncate, hipStream_t s);
+int launch_grid_reuse_window(const lzq_point& base, const lzq_window& base_win, const GridSpec& grid,
+                             const lzq_window_tables& wt, int64_t start, int64_t count, int32_t n_y, const double* d_P,
+                             double key_nz, double key_z_max, const double* d_work, int64_t stride, lzq_yield* d_out,
+                             hipStream_t s);
+
 // Longest-first launch order (lzq_propagator.hip): cost bins per point (0 = costliest, kCostBins
 // of them) and their histogram -> offs (kCostBins scratch) and order[n] (a counting sort: one
 // scan, one scatter; stable across bins, atomics order within one).  Sets lzq_last_error.

@@ -764,7 +764,7 @@ int lzq_yields_batch_window(const lzq_point* d_points, int64_t n, int32_t n_y, i
 namespace {
 // lzq_sweep_grid's argument checks and GridSpec (shared with lzq_sweep_grid_reuse)
 int make_grid(const lzq_point* base, const lzq_axis* axes, int32_t n_axes, int64_t start, int64_t count,
-              const lzq_yield* d_out, const char* who, lzq::GridSpec& g) {
+              const lzq_yield* d_out, const char* who, lzq::GridSpec& g, bool window_axes = false) {
   if (!base || n_axes < 0 || n_axes > LZQ_MAX_AXES || (n_axes > 0 && !axes) || start < 0 || count < 0 ||
       (count > 0 && !d_out))
     return fail(LZQ_EINVAL, "%s: bad arguments", who);
@@ -774,7 +774,9 @@ int make_grid(const lzq_point* base, const lzq_axis* axes, int32_t n_axes, int64
   bool mix = false, dpr = false;
   for (int a = n_axes - 1; a >= 0; --a) {
     const int32_t f = axes[a].field;
-    if (!((f >= 0 && f <= 14) || f == LZQ_F_DELTA_LZ || f == LZQ_F_M_MIX || f == LZQ_F_DPRIME))
+    // the fields of the window block: the *_window entry points only (grid_point skips them)
+    if (!((f >= 0 && f <= 14) || f == LZQ_F_DELTA_LZ || f == LZQ_F_M_MIX || f == LZQ_F_DPRIME ||
+          (window_axes && f >= LZQ_F_WIN_Y0 && f <= LZQ_F_WIN_TABLE)))
       return fail(LZQ_EINVAL, "%s: axis %d has unknown field %d", who, a, f);
     if (axes[a].n <= 0 || !axes[a].values) return fail(LZQ_EINVAL, "%s: axis %d is empty", who, a);
     mix |= f == LZQ_F_M_MIX;
@@ -792,7 +794,7 @@ int make_grid(const lzq_point* base, const lzq_axis* axes, int32_t n_axes, int64
                 (long long)(start + count), (long long)total);
   if (base->regime != LZQ_THERMAL && base->regime != LZQ_NONTHERMAL)
     return fail(LZQ_EUNSUPPORTED, "%s: regime must be thermal or nonthermal (fpy:376-384)", who);
-  return LZQ_OK;
+  return window_axes ? lzq::window_axes_check(axes, n_axes, who) : LZQ_OK;
 }
 
 // the fields quad_setup's y-grid and c depend on (lzq_sweep_grid_reuse's table axes)
@@ -916,10 +918,17 @@ int64_t lzq_sweep_grid_reuse_workspace(const lzq_axis* axes, int32_t n_axes, int
 static int sweep_grid_reuse_parts(const lzq_point* base, const lzq_axis* axes, int32_t n_axes, int64_t start,
                                   int64_t count, int32_t n_y, int32_t nz, double z_max, const double* d_P,
                                   double* d_work, int64_t work_doubles, lzq_yield* d_out, void* stream, int parts,
-                                  const char* fn) {
+                                  const char* fn, bool window_axes = false, const lzq_window* base_win = nullptr,
+                                  const lzq_window_tables* d_tables = nullptr) {
   lzq::GridSpec gs;
-  int rc = make_grid(base, axes, n_axes, start, count, d_out, fn, gs);
+  int rc = make_grid(base, axes, n_axes, start, count, d_out, fn, gs, window_axes);
   if (rc) return rc;
+  lzq_window_tables wt = {0, 0, nullptr, nullptr};
+  if (window_axes && (parts & 2)) {  // the integration half of a window grid
+    if (!base_win) return fail(LZQ_EINVAL, "%s: bad arguments", fn);
+    rc = lzq::window_tables_arg(d_tables, fn, wt);
+    if (rc) return rc;
+  }
   const int64_t need = lzq_sweep_grid_reuse_workspace(axes, n_axes, n_y);
   if (need < 0) return (int)need;
   const bool work = (parts & 1) || count > 0;
@@ -954,6 +963,9 @@ static int sweep_grid_reuse_parts(const lzq_point* base, const lzq_axis* axes, i
                          trunc);
     LZQ_HIP(hipGetLastError());
   }
+  if ((parts & 2) && count > 0 && base_win)  // the point's window from its block (lzq_window.hip)
+    return lzq::launch_grid_reuse_window(*base, *base_win, gs, wt, start, count, n_y, d_P, g.key.nz, g.key.z_max,
+                                         d_work, stride, d_out, (hipStream_t)stream);
   if ((parts & 2) && count > 0) {
     hipLaunchKernelGGL(lzq::grid_reuse_kernel, dim3((unsigned)nb), dim3(lzq::kBlock), 0, (hipStream_t)stream, *base, gs,
                        start, count, n_y, d_P, g.key, d_work, stride, d_out);
@@ -984,6 +996,52 @@ int lzq_sweep_grid_from_ztables(const lzq_point* base, const lzq_axis* axes, int
                                 const double* d_work, int64_t work_doubles, lzq_yield* d_out, void* stream) {
   return sweep_grid_reuse_parts(base, axes, n_axes, start, count, n_y, nz, z_max, d_P, const_cast<double*>(d_work),
                                 work_doubles, d_out, stream, 2, "lzq_sweep_grid_from_ztables");
+}
+
+int lzq_sweep_grid_window(const lzq_point* base, const lzq_window* base_win, const lzq_axis* axes, int32_t n_axes,
+                          int64_t start, int64_t count, int32_t n_y, int32_t nz, double z_max, const double* d_P,
+                          const lzq_window_tables* d_tables, lzq_yield* d_out, void* stream) {
+  if (!base_win) return fail(LZQ_EINVAL, "lzq_sweep_grid_window: bad arguments");
+  lzq::GridSpec gs;
+  int rc = make_grid(base, axes, n_axes, start, count, d_out, "lzq_sweep_grid_window", gs, true);
+  if (rc) return rc;
+  lzq_window_tables wt;
+  rc = lzq::window_tables_arg(d_tables, "lzq_sweep_grid_window", wt);
+  if (rc) return rc;
+  if (count == 0) return LZQ_OK;
+  int dev;
+  DevZGrid g;
+  rc = zgrid_for(nz, z_max, g, &dev);
+  if (rc) return rc;
+  if (blocks_for(count, lzq::kWavesPerBlock) > kMaxGrid)
+    return fail(LZQ_EINVAL, "lzq_sweep_grid_window: count too large for one launch");
+  return lzq::launch_yields_grid_window(g_exp_variant, g.is_default, *base, *base_win, gs, wt, start, count, n_y, d_P,
+                                        g.zt, g.nzp, exp_table(dev), d_out, g.monotone ? g_truncate : 0,
+                                        (hipStream_t)stream);
+}
+
+int lzq_sweep_grid_reuse_window(const lzq_point* base, const lzq_window* base_win, const lzq_axis* axes,
+                                int32_t n_axes, int64_t start, int64_t count, int32_t n_y, int32_t nz, double z_max,
+                                const double* d_P, double* d_work, int64_t work_doubles,
+                                const lzq_window_tables* d_tables, lzq_yield* d_out, void* stream) {
+  // an empty range validates only, as lzq_sweep_grid_reuse (parts = 2 builds nothing)
+  return sweep_grid_reuse_parts(base, axes, n_axes, start, count, n_y, nz, z_max, d_P, d_work, work_doubles, d_out,
+                                stream, count == 0 ? 2 : 3, "lzq_sweep_grid_reuse_window", true, base_win, d_tables);
+}
+
+int lzq_sweep_grid_ztables_window(const lzq_point* base, const lzq_axis* axes, int32_t n_axes, int32_t n_y,
+                                  int32_t nz, double z_max, double* d_work, int64_t work_doubles, void* stream) {
+  return sweep_grid_reuse_parts(base, axes, n_axes, 0, 0, n_y, nz, z_max, nullptr, d_work, work_doubles, nullptr,
+                                stream, 1, "lzq_sweep_grid_ztables_window", true);
+}
+
+int lzq_sweep_grid_from_ztables_window(const lzq_point* base, const lzq_window* base_win, const lzq_axis* axes,
+                                       int32_t n_axes, int64_t start, int64_t count, int32_t n_y, int32_t nz,
+                                       double z_max, const double* d_P, const double* d_work, int64_t work_doubles,
+                                       const lzq_window_tables* d_tables, lzq_yield* d_out, void* stream) {
+  return sweep_grid_reuse_parts(base, axes, n_axes, start, count, n_y, nz, z_max, d_P, const_cast<double*>(d_work),
+                                work_doubles, d_out, stream, 2, "lzq_sweep_grid_from_ztables_window", true, base_win,
+                                d_tables);
 }
 
 int lzq_p_closed_form(const double* d_lambda, int64_t n, double* d_P, void* stream) {

@@ -7,7 +7,8 @@
 // selects are used here, each rounded on its own (-ffp-contract=off), so the host build of these
 // functions gives the device's q and table values bit for bit (tests/test_window_host.py,
 // tests/test_gpu_window.py); the exponential on top of q is the caller's (libm on the host, exp_sc
-// in the kernels).
+// in the kernels).  The decode of a grid sweep's flat index into a point's block (window_grid_block)
+// is here too, one definition for the kernels and for lzq_window_grid_blocks_host.
 #pragma once
 #include "../../include/lzq.h"
 #include "lzq_exp2.h"
@@ -92,5 +93,68 @@ LZQ_HD double window_table_W(const WinParams& p, double v) {
   const double uk = p.u[lo], Wk = p.W[lo];
   return Wk + (v - uk) * ((p.W[lo + 1] - Wk) / (p.u[lo + 1] - uk));
 }
+
+// ---- window axes of a grid sweep (include/lzq.h LZQ_F_WIN_*) -------------------------------------
+LZQ_HD bool window_field(int32_t f) { return f >= LZQ_F_WIN_Y0 && f <= LZQ_F_WIN_TABLE; }
+
+// The block fields an axis field writes, as a bit mask (0: not a window field): two axes whose
+// masks meet write the same field, which the entry points refuse.
+LZQ_HD uint32_t window_field_mask(int32_t f) {
+  switch (f) {
+    case LZQ_F_WIN_Y0: return 1u;
+    case LZQ_F_WIN_HALF_WIDTH: return 2u;
+    case LZQ_F_WIN_SIGMA_LO: return 4u;
+    case LZQ_F_WIN_SIGMA_HI: return 8u;
+    case LZQ_F_WIN_SIGMA: return 4u | 8u;
+    case LZQ_F_WIN_SCALE: return 16u;
+    case LZQ_F_WIN_TABLE: return 32u;
+    default: return 0u;
+  }
+}
+
+// A table axis value: the double is tested before it is converted (an int32 conversion of a NaN or
+// of a value out of range is undefined); anything but an integer in [0, 2^31) gives -1, which
+// window_block_error refuses for a table-kind block whatever n_tables is.
+LZQ_HD int32_t window_table_value(double v) {
+  if (!(v >= 0.0 && v < 2147483648.0)) return -1;
+  const int32_t t = (int32_t)v;
+  return (double)t == v ? t : -1;
+}
+
+LZQ_HD void window_set_field(lzq_window& w, int32_t f, double v) {
+  switch (f) {  // explicit switch, as set_field (lzq_quad.h): no runtime-indexed store
+    case LZQ_F_WIN_Y0: w.y0 = v; break;
+    case LZQ_F_WIN_HALF_WIDTH: w.half_width = v; break;
+    case LZQ_F_WIN_SIGMA_LO: w.sigma_lo = v; break;
+    case LZQ_F_WIN_SIGMA_HI: w.sigma_hi = v; break;
+    case LZQ_F_WIN_SIGMA: w.sigma_lo = v; w.sigma_hi = v; break;
+    case LZQ_F_WIN_SCALE: w.scale = v; break;
+    case LZQ_F_WIN_TABLE: w.table = window_table_value(v); break;
+    default: break;
+  }
+}
+
+// The window block of flat grid index idx: base with the window axes' values written into it, a
+// second pass over the axes next to grid_point's (lzq_quad.h) that reads the window fields only.
+// Grid: n_axes, field[], n[], stride[] (int64, C order) and values[] -- lzq_quad.h's GridSpec in the
+// kernels (values in device memory), HostWinGrid below on the host.  64-bit index arithmetic.
+template <class Grid>
+LZQ_HD lzq_window window_grid_block(const lzq_window& base, const Grid& g, int64_t idx) {
+  lzq_window w = base;
+  for (int a = 0; a < g.n_axes; ++a) {
+    if (!window_field(g.field[a])) continue;
+    const int64_t c = (idx / g.stride[a]) % g.n[a];
+    window_set_field(w, g.field[a], g.values[a][c]);
+  }
+  return w;
+}
+
+struct HostWinGrid {
+  int32_t n_axes;
+  int32_t field[LZQ_MAX_AXES];
+  int64_t n[LZQ_MAX_AXES];
+  int64_t stride[LZQ_MAX_AXES];
+  const double* values[LZQ_MAX_AXES];
+};
 
 }  // namespace lzq

@@ -1,6 +1,9 @@
 // lzq_window.hip -- the quadrature kernels whose source activity window W(y) is a per-point block
 // (include/lzq.h lzq_window; PAPER §10 step 4: the Gaussian proxy of fpy:262 replaced by a plateau
-// family or a tabulated profile), W(y) alone, and the window's host build.
+// family or a tabulated profile), W(y) alone, and the window's host build.  Two forms of each
+// quadrature kernel: explicit records (points and blocks in device arrays), and the grid form, where
+// the point (grid_point) and its block (lzq_window.h window_grid_block: the base block with the
+// window axes' values) are decoded from the flat grid index in the kernel.
 //
 // The kernels are the headline ones (lzq_quad.h: same setup, same z-sum, same y-loop, same
 // butterfly, same epilogue) with the window factor of y_factors taken from the block parked in the
@@ -11,6 +14,7 @@
 
 #include <math.h>
 #include <stdio.h>
+#include <string.h>
 
 #define LZQ_QUAD_CONST_LINKAGE static
 #include "lzq_quad.h"
@@ -110,6 +114,78 @@ __global__ __launch_bounds__(kBlock, LZQ_REUSE_MIN_WAVES) void points_reuse_wind
     lzq_yield o = epilogue_finish(slots[w].e, Y_B);
     if (!match) o.Y_B = o.rho_B_kg_m3 = o.DM_over_B = __builtin_nan("");
     out[idx] = o;
+  }
+}
+
+// lzq_sweep_grid_window: yields_points_window_kernel with the point (grid_point) and its block
+// (window_grid_block) decoded from the flat index start + local, once per wavefront, before the
+// z-loop; both end in the wave's slot, so nothing new is live across it.  A block the decode leaves
+// unusable (a NaN, sigma <= 0, a table value that is no integer in range, ...) is kWinBad in
+// window_params: NaN yields, no table read.
+template <int YB, int EXPV, int NZ>
+__global__ __launch_bounds__(kBlock, LZQ_MIN_WAVES) void yields_grid_window_kernel(
+    lzq_point base, lzq_window base_win, GridSpec grid, lzq_window_tables wt, int64_t start, int64_t count,
+    int32_t n_y, const double* __restrict__ Pov, const ZNode* __restrict__ zt, int32_t nzp,
+    const double* __restrict__ gtab, lzq_yield* __restrict__ out, int truncate) {
+  __shared__ double lds_tab[kTabN];
+  const double* tab = stage_table<EXPV>(gtab, lds_tab);
+  __shared__ WinWaveSlot slots[kWavesPerBlock];
+  const int lane = threadIdx.x & (kWaveSize - 1);
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t local = (int64_t)blockIdx.x * kWavesPerBlock + w;
+  if (local >= count) return;  // wave-uniform
+  {
+    lzq_point pt;
+    const double Pg = grid_point(base, grid, start + local, pt);
+    const double P = Pov ? Pov[local] : Pg;
+    const lzq_window blk = window_grid_block(base_win, grid, start + local);
+    park_window(slots[w], quad_setup(pt, P, pt.T_min_over_Tp * pt.T_p_GeV, pt.T_max_over_Tp * pt.T_p_GeV, n_y),
+                epilogue_pre(pt, P), window_params(blk, wt.n_tables, wt.n_knots, wt.u, wt.W), lane);
+  }
+  // inlined at this call whatever the inliner's budget says after the two decodes: yb_wave keeps its
+  // wave index in a scalar register, which only the kernel's own (readfirstlane) w can supply
+  double Y_B;
+  [[clang::always_inline]] Y_B = yb_wave<YB, EXPV, kYbDense, NZ, SlotWindow>(slots, w, zt, nzp, tab, truncate);
+  if (lane == 0) out[local] = epilogue_finish(slots[w].e, Y_B);
+}
+
+// a grid point's z-sum table (lzq_kernels.hip table_of: the table axes' coordinates by tstride;
+// window axes lie between them with tstride 0)
+__device__ __forceinline__ int64_t win_table_of(const GridSpec& g, int64_t idx) {
+  int64_t t = 0;
+  for (int a = 0; a < g.n_axes; ++a) t += ((idx / g.stride[a]) % g.n[a]) * g.tstride[a];
+  return t;
+}
+
+// lzq_sweep_grid_from_ztables_window: points_reuse_window_kernel with the point, its block and its
+// table index decoded from the flat index
+__global__ __launch_bounds__(kBlock, LZQ_REUSE_MIN_WAVES) void grid_reuse_window_kernel(
+    lzq_point base, lzq_window base_win, GridSpec grid, lzq_window_tables wt, int64_t start, int64_t count,
+    int32_t n_y, const double* __restrict__ Pov, double key_nz, double key_z_max, const double* __restrict__ Fw,
+    int64_t tstride, lzq_yield* __restrict__ out) {
+  __shared__ WinWaveSlot slots[kWavesPerBlock];
+  const int lane = threadIdx.x & (kWaveSize - 1);
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t local = (int64_t)blockIdx.x * kWavesPerBlock + w;
+  if (local >= count) return;
+  lzq_point pt;
+  const double Pg = grid_point(base, grid, start + local, pt);
+  const double P = Pov ? Pov[local] : Pg;
+  const QuadSetup qs = quad_setup(pt, P, pt.T_min_over_Tp * pt.T_p_GeV, pt.T_max_over_Tp * pt.T_p_GeV, n_y);
+  const double* F = Fw + win_table_of(grid, start + local) * tstride;
+  // match is wave-uniform: every lane formed the same setup
+  const bool match = qs.empty || (F[0] == qs.y_lo && F[1] == qs.y_hi && F[2] == (double)qs.n && F[3] == qs.cneg &&
+                                  F[4] == key_nz && F[5] == key_z_max);
+  const lzq_window blk = window_grid_block(base_win, grid, start + local);
+  park_window(slots[w], qs, epilogue_pre(pt, P), window_params(blk, wt.n_tables, wt.n_knots, wt.u, wt.W), lane);
+  double Y_B = 0.0;
+  if (match)  // (inlined here, as in the dense kernel)
+    [[clang::always_inline]] Y_B = yb_wave<kYB, kExpTable, kYbReuse, 0, SlotWindow>(slots, w, nullptr, 0, nullptr, 0,
+                                                                                      F + LZQ_REUSE_TABLE_HEADER);
+  if (lane == 0) {
+    lzq_yield o = epilogue_finish(slots[w].e, Y_B);
+    if (!match) o.Y_B = o.rho_B_kg_m3 = o.DM_over_B = __builtin_nan("");
+    out[local] = o;
   }
 }
 
@@ -239,6 +315,150 @@ int lzq_window_batch(const lzq_window* win, const lzq_window_tables* d_tables, c
 }
 
 }  // extern "C"
+
+namespace {
+
+// The axes of a host-side window grid call as window_grid_block reads them (C order strides); the
+// checks are lzq_sweep_grid's for the parts read here, and window_axes_check.
+int host_win_grid(const lzq_axis* axes, int32_t n_axes, const char* who, lzq::HostWinGrid& g, int64_t& total) {
+  char msg[256];
+  if (n_axes < 0 || n_axes > LZQ_MAX_AXES || (n_axes > 0 && !axes)) {
+    snprintf(msg, sizeof(msg), "%s: bad arguments", who);
+    return lzq_set_error(LZQ_EINVAL, msg);
+  }
+  g = lzq::HostWinGrid();
+  g.n_axes = n_axes;
+  total = 1;
+  for (int a = n_axes - 1; a >= 0; --a) {
+    const int32_t f = axes[a].field;
+    const bool win = lzq::window_field(f);
+    if (!(win || (f >= 0 && f <= 14) || f == LZQ_F_DELTA_LZ || f == LZQ_F_M_MIX || f == LZQ_F_DPRIME)) {
+      snprintf(msg, sizeof(msg), "%s: axis %d has unknown field %d", who, a, f);
+      return lzq_set_error(LZQ_EINVAL, msg);
+    }
+    if (axes[a].n <= 0 || (win && !axes[a].values)) {
+      snprintf(msg, sizeof(msg), "%s: axis %d is empty", who, a);
+      return lzq_set_error(LZQ_EINVAL, msg);
+    }
+    g.field[a] = f;
+    g.n[a] = axes[a].n;
+    g.values[a] = axes[a].values;
+    g.stride[a] = total;
+    if (total > INT64_MAX / axes[a].n) {
+      snprintf(msg, sizeof(msg), "%s: grid too large", who);
+      return lzq_set_error(LZQ_EINVAL, msg);
+    }
+    total *= axes[a].n;
+  }
+  return lzq::window_axes_check(axes, n_axes, who);
+}
+
+}  // namespace
+
+extern "C" {
+
+int lzq_window_grid_blocks_host(const lzq_window* base_win, const lzq_axis* axes, int32_t n_axes, int64_t start,
+                                int64_t count, lzq_window* out_blocks) {
+  if (!base_win || start < 0 || count < 0 || (count > 0 && !out_blocks))
+    return lzq_set_error(LZQ_EINVAL, "lzq_window_grid_blocks_host: bad arguments");
+  lzq::HostWinGrid g;
+  int64_t total;
+  const int rc = host_win_grid(axes, n_axes, "lzq_window_grid_blocks_host", g, total);
+  if (rc) return rc;
+  if (start > total || count > total - start) {
+    char msg[256];
+    snprintf(msg, sizeof(msg), "lzq_window_grid_blocks_host: range [%lld, %lld) outside grid of %lld points",
+             (long long)start, (long long)(start + count), (long long)total);
+    return lzq_set_error(LZQ_EINVAL, msg);
+  }
+  for (int64_t i = 0; i < count; ++i) out_blocks[i] = lzq::window_grid_block(*base_win, g, start + i);
+  return LZQ_OK;
+}
+
+int lzq_window_grid_check_host(const lzq_window* base_win, const lzq_axis* axes, int32_t n_axes,
+                               const lzq_window_tables* host_tables) {
+  if (!base_win) return lzq_set_error(LZQ_EINVAL, "lzq_window_grid_check_host: bad arguments");
+  lzq::HostWinGrid g;
+  int64_t total;
+  int rc = host_win_grid(axes, n_axes, "lzq_window_grid_check_host", g, total);
+  if (rc) return rc;
+  rc = lzq_window_check_host(base_win, 1, host_tables);  // the tables and the base block
+  if (rc) return rc;
+  const lzq_window_tables& t = host_tables ? *host_tables : kNoTables;
+  for (int a = 0; a < n_axes; ++a) {
+    if (!lzq::window_field(g.field[a])) continue;
+    for (int64_t c = 0; c < g.n[a]; ++c) {
+      lzq_window w = *base_win;
+      const double v = g.values[a][c];
+      lzq::window_set_field(w, g.field[a], v);
+      char msg[256];
+      if (g.field[a] == LZQ_F_WIN_TABLE && w.kind == LZQ_WIN_TABLE && (w.table < 0 || w.table >= t.n_tables)) {
+        snprintf(msg, sizeof(msg), "window axis %d (field %d), value %lld = %.17g: not an integer table index in [0, %d)",
+                 a, g.field[a], (long long)c, v, t.n_tables);
+        return lzq_set_error(LZQ_EINVAL, msg);
+      }
+      if (check_block(w, 0, t)) {
+        // check_block's message is "window 0: <what>"; keep the <what>
+        const char* what = lzq_last_error();
+        const char* colon = strchr(what, ':');
+        char tail[160];
+        snprintf(tail, sizeof(tail), "%s", colon ? colon + 2 : what);
+        snprintf(msg, sizeof(msg), "window axis %d (field %d), value %lld = %.17g: %s", a, g.field[a], (long long)c, v,
+                 tail);
+        return lzq_set_error(LZQ_EINVAL, msg);
+      }
+    }
+  }
+  return LZQ_OK;
+}
+
+}  // extern "C"
+
+int lzq::window_axes_check(const lzq_axis* axes, int32_t n_axes, const char* who) {
+  uint32_t seen = 0;
+  for (int a = 0; a < n_axes; ++a) {
+    const uint32_t m = window_field_mask(axes[a].field);
+    if (seen & m) {
+      char msg[256];
+      snprintf(msg, sizeof(msg), "%s: axis %d (field %d) writes a window field that an earlier axis writes", who, a,
+               axes[a].field);
+      return lzq_set_error(LZQ_EINVAL, msg);
+    }
+    seen |= m;
+  }
+  return LZQ_OK;
+}
+
+int lzq::launch_yields_grid_window(int exp_variant, bool default_grid, const lzq_point& base,
+                                   const lzq_window& base_win, const GridSpec& grid, const lzq_window_tables& wt,
+                                   int64_t start, int64_t count, int32_t n_y, const double* d_P, const ZNode* zt,
+                                   int32_t nzp, const double* gtab, lzq_yield* d_out, int truncate, hipStream_t s) {
+  const int64_t nb = (count + kWavesPerBlock - 1) / kWavesPerBlock;
+#define LZQ_GRID_WIN(EXPV, NZ)                                                                                   \
+  hipLaunchKernelGGL((yields_grid_window_kernel<kYB, EXPV, NZ>), dim3((unsigned)nb), dim3(kBlock), 0, s, base,  \
+                     base_win, grid, wt, start, count, n_y, d_P, zt, nzp, gtab, d_out, truncate)
+  if (exp_variant == kExpTable) {
+    if (default_grid) LZQ_GRID_WIN(kExpTable, kNZ);
+    else LZQ_GRID_WIN(kExpTable, 0);
+  } else {
+    if (default_grid) LZQ_GRID_WIN(kExpPoly11, kNZ);
+    else LZQ_GRID_WIN(kExpPoly11, 0);
+  }
+#undef LZQ_GRID_WIN
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? LZQ_OK : lzq_set_error(LZQ_EHIP, hipGetErrorString(e));
+}
+
+int lzq::launch_grid_reuse_window(const lzq_point& base, const lzq_window& base_win, const GridSpec& grid,
+                                  const lzq_window_tables& wt, int64_t start, int64_t count, int32_t n_y,
+                                  const double* d_P, double key_nz, double key_z_max, const double* d_work,
+                                  int64_t stride, lzq_yield* d_out, hipStream_t s) {
+  const int64_t nb = (count + kWavesPerBlock - 1) / kWavesPerBlock;
+  hipLaunchKernelGGL(grid_reuse_window_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, base, base_win, grid, wt, start,
+                     count, n_y, d_P, key_nz, key_z_max, d_work, stride, d_out);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? LZQ_OK : lzq_set_error(LZQ_EHIP, hipGetErrorString(e));
+}
 
 int lzq::window_tables_arg(const lzq_window_tables* d_tables, const char* who, lzq_window_tables& out) {
   out = d_tables ? *d_tables : kNoTables;

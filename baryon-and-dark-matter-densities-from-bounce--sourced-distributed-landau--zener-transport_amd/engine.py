@@ -38,7 +38,7 @@ class Engine:
         self._ztab_key = None  # the grid whose tables _zwork holds (Engine.sweep reuse)
         self._exp_variant = "table"
         self.last_reuse = None
-        self.last_yields_path = None  # the last Engine.yields call: "tables" (z-sums shared) or "dense"
+        self.last_yields_path = None  # the last Engine.yields / sweep call: "tables" (z-sums shared) or "dense"
         with torch.cuda.device(self.device):
             self._check(self.lib.lzq_init(self.device.index))
 
@@ -259,23 +259,44 @@ class Engine:
     def sweep(self, base_cfg, axes: Sequence[tuple], start: int, count: int, n_y: int = 8000,
               out: Optional[torch.Tensor] = None, P: Optional[float] = None,
               P_points: Optional[torch.Tensor] = None, reuse: bool = False, nz: int = _native.LZQ_NZ,
-              z_max: float = _native.LZQ_Z_MAX) -> torch.Tensor:
+              z_max: float = _native.LZQ_Z_MAX, window=None, window_tables=None) -> torch.Tensor:
         """axes: sequence of (field_name, values) (C order, last fastest); field names are
         the lzq_point double fields or 'delta_LZ' / 'm_mix' / 'dprime'.  P_points: optional
         per-point P override ([count], device), e.g. from lz_propagate (config C5).
         reuse: lzq_sweep_grid_reuse -- the z-sums computed once per combination of the grid's
         I_p / beta_over_H / T_p_GeV / T_min_over_Tp / T_max_over_Tp values and shared by the
         points (bit-identical results; NOT the dense headline path).
-        nz, z_max: the A/V kernel's z grid (fpy:141-156; main()'s default 1200, 30)."""
+        nz, z_max: the A/V kernel's z grid (fpy:141-156; main()'s default 1200, 30).
+        window: the source activity window W(y) of every point in place of the Gaussian proxy of fpy:262
+        (one block: a mapping, see window.to_window, or a 1-record WINDOW_DTYPE array); axes may then
+        carry the names of sweep.WINDOW_AXES, whose values are written into the block per point, decoded
+        from the flat index in the kernel like the point's own fields (lzq_sweep_grid_window and the
+        shared-z-sum twins; the z-sums do not depend on the window, so `reuse` applies as without one).
+        Host axis values are checked before any upload (window.grid_check; LzqError names the axis and
+        the value); values given as device tensors are not, and a block that cannot be evaluated then
+        gives NaN yields.  window_tables: the tabulated profiles of the table kind, as for yields."""
         nz, z_max = _native.zgrid(nz, z_max)
         if len(axes) > _native.LZQ_MAX_AXES:
             raise ValueError(f"at most {_native.LZQ_MAX_AXES} sweep axes")
+        win = d_wt = None
+        if window is not None:
+            d_wt = self.window_tables_to_device(window_tables)
+            rec = _window.to_window(window)
+            _window.grid_check(rec, [(n, v) for n, v in axes
+                                     if n in _native.WINDOW_FIELD and not isinstance(v, torch.Tensor)], d_wt.host)
+            win = _native.LzqWindow.from_buffer_copy(rec.tobytes())
+        elif window_tables is not None:
+            raise ValueError("sweep: window_tables without a window")
+        fields = dict(_native.FIELD, **_native.WINDOW_FIELD) if win is not None else _native.FIELD
+        for name, _ in axes:
+            if name not in fields:
+                if name in _native.WINDOW_FIELD:
+                    raise ValueError(f"sweep field {name!r} needs a window")
+                raise ValueError(f"unknown sweep field {name!r}")
         dev_vals = [self._f64(v).reshape(-1) for _, v in axes]
         arr = (_native.LzqAxis * max(1, len(axes)))()
         for a, ((name, _), t) in enumerate(zip(axes, dev_vals)):
-            if name not in _native.FIELD:
-                raise ValueError(f"unknown sweep field {name!r}")
-            arr[a].field = _native.FIELD[name]
+            arr[a].field = fields[name]
             arr[a].n = t.numel()
             arr[a].values = t.data_ptr()
         base = to_ctypes_point(to_point(base_cfg, P=P))
@@ -295,8 +316,9 @@ class Engine:
             # workspace stays bounded (REUSE_MAX_BYTES): otherwise the dense path, same bits
             tkey = None
             if reuse:
-                tkey = (bytes(base), tuple((n, np.asarray(v, dtype=np.float64).tobytes()) for n, v in axes), int(n_y),
-                        self._exp_variant, nz, z_max)
+                tkey = (bytes(base), tuple((n, t.cpu().numpy().tobytes() if isinstance(v, torch.Tensor)
+                                            else np.asarray(v, dtype=np.float64).tobytes())
+                                           for (n, v), t in zip(axes, dev_vals)), int(n_y), self._exp_variant, nz, z_max)
                 built = tkey == self._ztab_key
                 why = None if need * 8 <= REUSE_MAX_BYTES else f"{n_tables} z-sum tables exceed REUSE_MAX_BYTES"
                 if why is None and not built and not 0 < n_tables <= count:
@@ -304,22 +326,33 @@ class Engine:
                 if why:
                     _log.warning("lzq reuse_zsums: dense path (same bits): %s", why)
                     reuse = False
-            self.last_reuse = "tables" if reuse else "dense"
+            self.last_reuse = self.last_yields_path = "tables" if reuse else "dense"
+            # with a window: the *_window twins of the same three entry points (the window axes are
+            # skipped by the table half and decoded into the point's block by the integrating ones)
             if reuse:
                 if not built:
                     if self._zwork is None or self._zwork.numel() < need:
                         self._zwork = torch.empty(max(int(need), 1), dtype=torch.float64, device=self.device)
-                    self._check(self.lib.lzq_sweep_grid_ztables(ctypes.byref(base), arr, len(axes), int(n_y), nz,
-                                                                z_max, _vp(self._zwork), self._zwork.numel(),
-                                                                self._stream()))
+                    ztables = self.lib.lzq_sweep_grid_ztables if win is None else self.lib.lzq_sweep_grid_ztables_window
+                    self._check(ztables(ctypes.byref(base), arr, len(axes), int(n_y), nz, z_max, _vp(self._zwork),
+                                        self._zwork.numel(), self._stream()))
                     self._ztab_key = tkey
-                self._check(self.lib.lzq_sweep_grid_from_ztables(
-                    ctypes.byref(base), arr, len(axes), int(start), int(count), int(n_y), nz, z_max, _vp(Pp),
-                    _vp(self._zwork), self._zwork.numel(), _vp(out), self._stream()))
-            else:
+                if win is None:
+                    self._check(self.lib.lzq_sweep_grid_from_ztables(
+                        ctypes.byref(base), arr, len(axes), int(start), int(count), int(n_y), nz, z_max, _vp(Pp),
+                        _vp(self._zwork), self._zwork.numel(), _vp(out), self._stream()))
+                else:
+                    self._check(self.lib.lzq_sweep_grid_from_ztables_window(
+                        ctypes.byref(base), ctypes.byref(win), arr, len(axes), int(start), int(count), int(n_y), nz,
+                        z_max, _vp(Pp), _vp(self._zwork), self._zwork.numel(), d_wt.arg, _vp(out), self._stream()))
+            elif win is None:
                 self._check(self.lib.lzq_sweep_grid(ctypes.byref(base), arr, len(axes), int(start), int(count),
                                                       int(n_y), nz, z_max, _vp(Pp), _vp(out), self._stream()))
-        self._keepalive = dev_vals  # axis buffers must outlive the async launch
+            else:
+                self._check(self.lib.lzq_sweep_grid_window(ctypes.byref(base), ctypes.byref(win), arr, len(axes),
+                                                             int(start), int(count), int(n_y), nz, z_max, _vp(Pp),
+                                                             d_wt.arg, _vp(out), self._stream()))
+        self._keepalive = (dev_vals, d_wt)  # axis buffers (and window tables) must outlive the async launch
         return out
 
     # -- sweep fits, posteriors, observables, ranked points (lzq_fit_*, lzq_post_*, lzq_obs_*,

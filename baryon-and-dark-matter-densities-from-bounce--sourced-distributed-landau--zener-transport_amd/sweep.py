@@ -748,6 +748,19 @@ def profile_P(spec: SweepSpec, s: int, n: int, engine, cache: dict):
     return P
 
 
+def window_axes_collide(spec: SweepSpec) -> bool:
+    """Do two of the spec's axes write the same field of the window block (a repeated axis, or
+    window_sigma next to window_sigma_lo / _hi)?  The grid entry points refuse such a list
+    (include/lzq.h); make_compute then keeps the host-record path."""
+    seen = set()
+    for name, _ in spec.axes:
+        for f in WINDOW_AXES.get(name, ()):
+            if f in seen:
+                return True
+            seen.add(f)
+    return False
+
+
 def grid_axes_for_kernel(spec: SweepSpec):
     """The spec's axes for lzq_sweep_grid: a profile coupling axis has no lzq_point field, so it
     rides on P_chi_to_B, which the per-point P override replaces (the flat-index decode of the
@@ -755,18 +768,35 @@ def grid_axes_for_kernel(spec: SweepSpec):
     return [("P_chi_to_B" if n in PROFILE_FIELDS else n, v) for n, v in spec.axes]
 
 
-def make_compute(spec: SweepSpec, engine, reuse: bool = False) -> ComputeFn:
+def make_compute(spec: SweepSpec, engine, reuse: bool = False, window_host_records: bool = False) -> ComputeFn:
     """(start, count, out) -> None on the GPU: [coherent multi-crossing P ->] quadrature, or
     the ODE fallback (lzq_ode_batch) for sweeps over sigma_v / Gamma_wash / depletion (with or
     without crossings).  reuse: the quadrature's z-sums shared across points with the same
-    y-grid and A/V kernel (lzq_sweep_grid_reuse; bit-identical, not the dense headline path)."""
+    y-grid and A/V kernel (lzq_sweep_grid_reuse; bit-identical, not the dense headline path).
+    window_host_records: a window spec through explicit host-built records even where the grid
+    entry points would take it (the same bits; tools/bench_window.py's baseline)."""
     pcache = {}   # the profile's device splines, built once per sweep
     check_window_spec(spec)
     if spec.window is not None:
-        # explicit point records, as the ODE specs', each with its window block; with reuse the
-        # z-sums (which no window enters) are shared by the points equal in _native.ZSUM_KEY
         d_tables = engine.window_tables_to_device(spec.window.host_tables())
+        grid_regime = int(to_point(spec.base)["regime"][0]) in (_native.THERMAL, _native.NONTHERMAL)
+        # (the grid entry points refuse a base of another regime, whose rows are NaN from records)
+        if not window_axes_collide(spec) and grid_regime and not window_host_records:
+            # the grid entry points: the window axes ride in the axis list and each point's block is
+            # decoded from the flat index in the kernel, like its other fields (Engine.sweep(window=))
+            def compute_window_grid(s, n, out):
+                P_points = coherent_P(spec, s, n, engine) if spec.crossings is not None else None
+                if spec.profile is not None:
+                    P_points = profile_P(spec, s, n, engine, pcache)   # the per-point override
+                engine.sweep(spec.base, grid_axes_for_kernel(spec), s, n, n_y=spec.n_y, out=out, P_points=P_points,
+                             reuse=reuse, nz=spec.nz, z_max=spec.z_max, window=spec.window.block,
+                             window_tables=d_tables)
+            return compute_window_grid
 
+        # two axes write one field of the block (the entry points refuse that): explicit point
+        # records, as the ODE specs', each with its window block (window_records resolves the
+        # collision: the earlier axis wins); with reuse the z-sums (which no window enters) are shared by
+        # the points equal in _native.ZSUM_KEY
         def compute_window(s, n, out):
             pts, _ = grid_records(spec, s, n, engine)
             P_points = coherent_P(spec, s, n, engine) if spec.crossings is not None else None

@@ -7,6 +7,7 @@ through engine.Engine.yields(window=...) and Engine.window.
 from __future__ import annotations
 
 import ctypes
+import re
 from typing import Optional
 
 import numpy as np
@@ -143,3 +144,51 @@ def eval_host(window, ys, tables=None) -> tuple:
     _native.check(lib.lzq_window_eval_host(ctypes.byref(blk), None if t is None else ctypes.byref(t), y.ctypes.data,
                                            y.size, q.ctypes.data, W.ctypes.data), lib)
     return q, W
+
+
+def _host_axes(axes):
+    """(lzq_axis array, keep-alive list) for (name, values) axes with HOST values: the window axes
+    (_native.WINDOW_FIELD; sweep.WINDOW_AXES) carry their values, the others only their length."""
+    arr = (_native.LzqAxis * max(1, len(axes)))()
+    keep = []
+    for a, (name, vals) in enumerate(axes):
+        if name in _native.WINDOW_FIELD:
+            v = np.ascontiguousarray(vals, dtype=np.float64).reshape(-1)
+            keep.append(v)
+            arr[a].field, arr[a].n, arr[a].values = _native.WINDOW_FIELD[name], v.size, v.ctypes.data
+        else:
+            field = name if isinstance(name, int) else _native.FIELD.get(name)
+            if field is None:
+                raise ValueError(f"unknown sweep field {name!r}")
+            arr[a].field, arr[a].n, arr[a].values = field, len(vals), None
+    return arr, keep
+
+
+def grid_blocks(base, axes, start: int, count: int) -> np.ndarray:
+    """The window blocks (WINDOW_DTYPE) of flat grid indices [start, start + count) of base x axes
+    (C order, last axis fastest): the library's host build of the decode the grid kernels run
+    (lzq_window_grid_blocks_host; csrc/lzq_window.h window_grid_block).  No GPU."""
+    lib = _native.load()
+    blk = _native.LzqWindow.from_buffer_copy(to_window(base).tobytes())
+    arr, keep = _host_axes(axes)
+    out = np.zeros(int(count), dtype=_native.WINDOW_DTYPE)
+    _native.check(lib.lzq_window_grid_blocks_host(ctypes.byref(blk), arr, len(axes), int(start), int(count),
+                                                  out.ctypes.data), lib)
+    return out
+
+
+def grid_check(base, axes, tables: Optional[WindowTables] = None) -> None:
+    """Every refusal of include/lzq.h for the blocks of the grid base x axes, from the base block and
+    each window axis's values on their own (lzq_window_grid_check_host): raises _native.LzqError
+    naming the axis and the value.  No GPU."""
+    lib = _native.load()
+    blk = _native.LzqWindow.from_buffer_copy(to_window(base).tobytes())
+    arr, keep = _host_axes(axes)
+    t = None if tables is None else tables.ctypes_host()
+    rc = lib.lzq_window_grid_check_host(ctypes.byref(blk), arr, len(axes), None if t is None else ctypes.byref(t))
+    if rc:
+        msg = (lib.lzq_last_error() or b"").decode()
+        m = re.match(r"window axis (\d+) ", msg)
+        if m:
+            msg = f"axis {axes[int(m.group(1))][0]!r}: {msg}"
+        raise _native.LzqError(rc, msg)

@@ -110,7 +110,12 @@ enum lzq_field {
   LZQ_F_I_P = 5, LZQ_F_G_STAR = 6, LZQ_F_G_STAR_S = 7, LZQ_F_P = 8, LZQ_F_SIGMA_Y = 9,
   LZQ_F_FLUX = 10, LZQ_F_T_MAX_OVER_TP = 11, LZQ_F_T_MIN_OVER_TP = 12, LZQ_F_Y_CHI_INIT = 13,
   LZQ_F_N_CHI_AT_TP = 14,
-  LZQ_F_DELTA_LZ = 32, LZQ_F_M_MIX = 33, LZQ_F_DPRIME = 34
+  LZQ_F_DELTA_LZ = 32, LZQ_F_M_MIX = 33, LZQ_F_DPRIME = 34,
+  /* fields of the point's window block (lzq_window below), accepted only by the *_window grid
+   * entry points; every other one refuses them as unknown fields */
+  LZQ_F_WIN_Y0 = 64, LZQ_F_WIN_HALF_WIDTH = 65, LZQ_F_WIN_SIGMA_LO = 66, LZQ_F_WIN_SIGMA_HI = 67,
+  LZQ_F_WIN_SIGMA = 68 /* sigma_lo and sigma_hi */, LZQ_F_WIN_SCALE = 69,
+  LZQ_F_WIN_TABLE = 70 /* table, from a double holding an integer */
 };
 
 #define LZQ_MAX_AXES 8
@@ -312,6 +317,48 @@ int lzq_yields_batch_reuse_window(const lzq_point* d_points, int64_t n, int32_t 
                                   const double* d_P, const int64_t* d_rep, const int32_t* d_table_index,
                                   int64_t n_tables, double* d_work, int64_t work_doubles, const lzq_window* d_win,
                                   const lzq_window_tables* d_tables, lzq_yield* d_out, void* stream);
+/* Cartesian sweeps whose points carry a window: lzq_sweep_grid and the shared-z-sum entry points
+ * with point i's window = *base_win (a host struct) with the values of the grid's window axes
+ * (LZQ_F_WIN_*) written into it, decoded from the flat index inside the kernel like the point's
+ * own fields (csrc/lzq_window.h window_grid_block: the one definition host and device build); the
+ * point's source_shape_sigma_y is not read.  LZQ_F_WIN_SIGMA writes sigma_lo and sigma_hi;
+ * LZQ_F_WIN_TABLE takes a double that must hold an integer (tested as a double before it is
+ * converted; anything else gives table = -1, which a table-kind block is refused for).  Two axes
+ * that write the same block field (a duplicate, or LZQ_F_WIN_SIGMA next to _SIGMA_LO / _SIGMA_HI)
+ * are LZQ_EINVAL; every other argument check is lzq_sweep_grid's.  Axis values live in device
+ * memory and are not checked at launch: a point whose decoded block is one of the refusals above
+ * gets NaN yields and reads no table (check host copies first with lzq_window_grid_check_host).
+ * With no window axis and a LZQ_WIN_GAUSS base block whose sigma_hi is the point's
+ * source_shape_sigma_y the yields are lzq_sweep_grid's bits; for any axes they are those of
+ * lzq_yields_batch_window on the decoded points and blocks.
+ * The z-sum tables do not depend on the window: window axes contribute no table
+ * (lzq_sweep_grid_reuse_workspace counts none for them), and lzq_sweep_grid_ztables_window is
+ * lzq_sweep_grid_ztables accepting (and skipping) the window fields, so that a table's index is
+ * formed from the strides of the whole axis list, as lzq_sweep_grid_from_ztables_window forms it. */
+int lzq_sweep_grid_window(const lzq_point* base, const lzq_window* base_win, const lzq_axis* axes, int32_t n_axes,
+                          int64_t start, int64_t count, int32_t n_y, int32_t nz, double z_max, const double* d_P,
+                          const lzq_window_tables* d_tables, lzq_yield* d_out, void* stream);
+int lzq_sweep_grid_reuse_window(const lzq_point* base, const lzq_window* base_win, const lzq_axis* axes,
+                                int32_t n_axes, int64_t start, int64_t count, int32_t n_y, int32_t nz, double z_max,
+                                const double* d_P, double* d_work, int64_t work_doubles,
+                                const lzq_window_tables* d_tables, lzq_yield* d_out, void* stream);
+int lzq_sweep_grid_ztables_window(const lzq_point* base, const lzq_axis* axes, int32_t n_axes, int32_t n_y,
+                                  int32_t nz, double z_max, double* d_work, int64_t work_doubles, void* stream);
+int lzq_sweep_grid_from_ztables_window(const lzq_point* base, const lzq_window* base_win, const lzq_axis* axes,
+                                       int32_t n_axes, int64_t start, int64_t count, int32_t n_y, int32_t nz,
+                                       double z_max, const double* d_P, const double* d_work, int64_t work_doubles,
+                                       const lzq_window_tables* d_tables, lzq_yield* d_out, void* stream);
+/* The host build of that decode: out_blocks[i] = the block of flat grid index start + i, i < count
+ * (64-bit throughout).  axes[a].values are HOST arrays here and are read only for the window
+ * axes (the others need their n alone).  No GPU. */
+int lzq_window_grid_blocks_host(const lzq_window* base_win, const lzq_axis* axes, int32_t n_axes, int64_t start,
+                                int64_t count, lzq_window* out_blocks);
+/* Host-side check of a window grid (HOST axis values): lzq_window_check_host on *base_win and the
+ * tables, then every value of every window axis substituted into *base_win on its own -- a block's
+ * refusals are per field, so this covers every block of the grid without a pass over it.  The
+ * message names the axis (its position in axes) and the value. */
+int lzq_window_grid_check_host(const lzq_window* base_win, const lzq_axis* axes, int32_t n_axes,
+                               const lzq_window_tables* host_tables);
 /* The ODE entry points below take no window: their source term keeps the reference's Gaussian
  * (fpy:226-228).  Engine.ode and the facade's ODE operators raise when given another one. */
 
