@@ -95,6 +95,19 @@ WINDOW_DTYPE = np.dtype([("kind", "<i4"), ("table", "<i4")] + [(n, "<f8") for n 
 assert ctypes.sizeof(LzqWindow) == 48 == WINDOW_DTYPE.itemsize and ctypes.sizeof(LzqWindowTables) == 24
 
 
+class LzqSolve(ctypes.Structure):  # struct lzq_solve: one parameter solved per grid point for a target yield
+    _fields_ = [("field", ctypes.c_int32), ("target_field", ctypes.c_int32), ("lo", ctypes.c_double),
+                ("hi", ctypes.c_double), ("target", ctypes.c_double), ("xtol", ctypes.c_double),
+                ("max_evals", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(LzqSolve) == 48
+SOLVE_RESULT_FIELDS = ("x", "x_lo", "x_hi", "residual", "evals", "status")  # struct lzq_solve_result
+SOLVE_OK, SOLVE_MAX_EVALS, SOLVE_NO_BRACKET, SOLVE_NAN, SOLVE_BAD_TABLE = range(5)  # enum lzq_solve_status
+SOLVE_STATUS = {0: "ok", 1: "max_evals", 2: "no_bracket", 3: "nan", 4: "bad_table"}
+SOLVE_MIN_EVALS, SOLVE_MAX_EVALS_CAP = 2, 256
+
+
 class LzqOdeParams(ctypes.Structure):
     _fields_ = [("sigma_v_chi_GeV_m2", ctypes.c_double), ("Gamma_wash_over_H", ctypes.c_double),
                 ("deplete_DM_from_source", ctypes.c_int32), ("reserved", ctypes.c_int32)]
@@ -179,6 +192,7 @@ EXPORTS = ("lzq_abi_version", "lzq_last_error", "lzq_init", "lzq_zgrid_init", "l
            "lzq_yields_batch_reuse_window",
            "lzq_sweep_grid_window", "lzq_sweep_grid_reuse_window", "lzq_sweep_grid_ztables_window",
            "lzq_sweep_grid_from_ztables_window", "lzq_window_grid_blocks_host", "lzq_window_grid_check_host",
+           "lzq_sweep_grid_solve", "lzq_solve_check_host",
            "lzq_lz_propagate", "lzq_lz_propagate_v", "lzq_ode_tables", "lzq_ode_integrate", "lzq_ode_integrate_shared", "lzq_ode_rows", "lzq_ode_integrate_rows", "lzq_ode_integrate_tp", "lzq_ode_quadrature", "lzq_ode_batch",
            "lzq_ode_aov_T", "lzq_ode_rhs", "lzq_profile_splines", "lzq_profile_crossings",
            "lzq_lz_propagate_profile",
@@ -257,6 +271,9 @@ def load(path: str | None = None):
                                                      d, vp, vp, i64, P(LzqWindowTables), vp, vp]
     L.lzq_window_grid_blocks_host.argtypes = [P(LzqWindow), P(LzqAxis), i32, i64, i64, vp]
     L.lzq_window_grid_check_host.argtypes = [P(LzqWindow), P(LzqAxis), i32, P(LzqWindowTables)]
+    L.lzq_sweep_grid_solve.argtypes = [P(LzqPoint), P(LzqWindow), P(LzqAxis), i32, P(LzqSolve), i64, i64, i32, i32, d,
+                                       vp, vp, i64, P(LzqWindowTables), vp, vp, vp]
+    L.lzq_solve_check_host.argtypes = [P(LzqSolve), P(LzqWindow), P(LzqAxis), i32]
     L.lzq_lz_propagate.argtypes = [vp, vp, vp, i64, i32, d, d, i32, vp, vp]
     L.lzq_lz_propagate_v.argtypes = [vp, vp, vp, vp, i64, i32, d, i32, vp, vp]
     L.lzq_ode_tables.argtypes = [vp, i64, vp, vp, i32, i32, d, vp, vp, i64, vp, vp]

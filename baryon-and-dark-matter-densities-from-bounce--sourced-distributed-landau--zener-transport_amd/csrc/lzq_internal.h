@@ -62,6 +62,13 @@ int launch_grid_reuse_window(const lzq_point& base, const lzq_window& base_win, 
                              double key_nz, double key_z_max, const double* d_work, int64_t stride, lzq_yield* d_out,
                              hipStream_t s);
 
+// lzq_solve.hip: lzq_sweep_grid_solve's kernel, one wavefront per grid point on the z-sum tables of
+// lzq_sweep_grid_ztables[_window] (grid with tstride set); base_win NULL: the point's Gaussian.
+int launch_grid_solve(const lzq_point& base, const lzq_window* base_win, const GridSpec& grid,
+                      const lzq_window_tables& wt, const lzq_solve& solve, int64_t start, int64_t count, int32_t n_y,
+                      const double* d_P, double key_nz, double key_z_max, const double* d_work, int64_t stride,
+                      lzq_yield* d_out, lzq_solve_result* d_sol, hipStream_t s);
+
 // Longest-first launch order (lzq_propagator.hip): cost bins per point (0 = costliest, kCostBins
 // of them) and their histogram -> offs (kCostBins scratch) and order[n] (a counting sort: one
 // scan, one scatter; stable across bins, atomics order within one).  Sets lzq_last_error.

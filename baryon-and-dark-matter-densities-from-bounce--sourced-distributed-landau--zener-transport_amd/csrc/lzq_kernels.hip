@@ -764,14 +764,16 @@ int lzq_yields_batch_window(const lzq_point* d_points, int64_t n, int32_t n_y, i
 namespace {
 // lzq_sweep_grid's argument checks and GridSpec (shared with lzq_sweep_grid_reuse)
 int make_grid(const lzq_point* base, const lzq_axis* axes, int32_t n_axes, int64_t start, int64_t count,
-              const lzq_yield* d_out, const char* who, lzq::GridSpec& g, bool window_axes = false) {
+              const lzq_yield* d_out, const char* who, lzq::GridSpec& g, bool window_axes = false,
+              int32_t solve_field = -1) {
   if (!base || n_axes < 0 || n_axes > LZQ_MAX_AXES || (n_axes > 0 && !axes) || start < 0 || count < 0 ||
       (count > 0 && !d_out))
     return fail(LZQ_EINVAL, "%s: bad arguments", who);
   memset(&g, 0, sizeof(g));
   g.n_axes = n_axes;
   int64_t total = 1;
-  bool mix = false, dpr = false;
+  // (a solve for one of m_mix / dprime stands for its axis)
+  bool mix = solve_field == LZQ_F_M_MIX, dpr = solve_field == LZQ_F_DPRIME;
   for (int a = n_axes - 1; a >= 0; --a) {
     const int32_t f = axes[a].field;
     // the fields of the window block: the *_window entry points only (grid_point skips them)
@@ -1042,6 +1044,48 @@ int lzq_sweep_grid_from_ztables_window(const lzq_point* base, const lzq_window* 
   return sweep_grid_reuse_parts(base, axes, n_axes, start, count, n_y, nz, z_max, d_P, const_cast<double*>(d_work),
                                 work_doubles, d_out, stream, 2, "lzq_sweep_grid_from_ztables_window", true, base_win,
                                 d_tables);
+}
+
+// lzq_sweep_grid_from_ztables[_window]'s checks and table strides, then the solve kernel (lzq_solve.hip)
+int lzq_sweep_grid_solve(const lzq_point* base, const lzq_window* base_win, const lzq_axis* axes, int32_t n_axes,
+                         const lzq_solve* solve, int64_t start, int64_t count, int32_t n_y, int32_t nz, double z_max,
+                         const double* d_P, const double* d_work, int64_t work_doubles,
+                         const lzq_window_tables* d_tables, lzq_yield* d_out, lzq_solve_result* d_sol, void* stream) {
+  const char* fn = "lzq_sweep_grid_solve";
+  if (!solve || (count > 0 && !d_sol)) return fail(LZQ_EINVAL, "%s: bad arguments", fn);
+  int rc = lzq_solve_check_host(solve, base_win, axes, n_axes);
+  if (rc) return rc;
+  const int32_t sf = solve->field;
+  if (d_P && (sf == LZQ_F_P || sf == LZQ_F_DELTA_LZ || sf == LZQ_F_M_MIX || sf == LZQ_F_DPRIME))
+    return fail(LZQ_EINVAL, "%s: a per-point P override (d_P) together with a solve for P or an LZ field", fn);
+  lzq::GridSpec gs;
+  rc = make_grid(base, axes, n_axes, start, count, d_out, fn, gs, base_win != nullptr, sf);
+  if (rc) return rc;
+  lzq_window_tables wt = {0, 0, nullptr, nullptr};
+  if (base_win) {
+    rc = lzq::window_tables_arg(d_tables, fn, wt);
+    if (rc) return rc;
+  }
+  const int64_t need = lzq_sweep_grid_reuse_workspace(axes, n_axes, n_y);
+  if (need < 0) return (int)need;
+  if (count > 0 && (!d_work || work_doubles < need))
+    return fail(LZQ_EINVAL, "%s: workspace of %lld doubles < %lld needed", fn, (long long)work_doubles,
+                (long long)need);
+  if (count == 0) return LZQ_OK;
+  int dev;
+  DevZGrid g;
+  rc = zgrid_for(nz, z_max, g, &dev);
+  if (rc) return rc;
+  int64_t ts = 1;
+  for (int a = gs.n_axes - 1; a >= 0; --a)
+    if (ztable_field(gs.field[a])) {
+      gs.tstride[a] = ts;
+      ts *= gs.n[a];
+    }
+  const int64_t stride = (n_y > LZQ_NY_MIN ? n_y : LZQ_NY_MIN) + lzq::kTabHdr;
+  if (blocks_for(count, lzq::kWavesPerBlock) > kMaxGrid) return fail(LZQ_EINVAL, "%s: too large for one launch", fn);
+  return lzq::launch_grid_solve(*base, base_win, gs, wt, *solve, start, count, n_y, d_P, g.key.nz, g.key.z_max,
+                                d_work, stride, d_out, d_sol, (hipStream_t)stream);
 }
 
 int lzq_p_closed_form(const double* d_lambda, int64_t n, double* d_P, void* stream) {

@@ -19,45 +19,10 @@
 #define LZQ_QUAD_CONST_LINKAGE static
 #include "lzq_quad.h"
 #include "lzq_internal.h"
+#include "lzq_quad_window.h"  // window_W, WinWaveSlot, SlotWindow, park_window, win_table_of
 #include "lzq_window.h"
 
 namespace lzq {
-
-// W(y) on the device: the table kind interpolates, the others take the quadrature's exponential
-// of -q^2/2.  kind is wave-uniform (one block per wavefront / per launch).
-__device__ __forceinline__ double window_W(const WinParams& p, int32_t kind, double y) {
-  if (kind == LZQ_WIN_TABLE) return window_table_W(p, window_v(p, y));
-  if (kind == kWinBad) return __builtin_nan("");
-  const double q = window_q(p, kind, y);
-  return exp_sc(-0.5 * (q * q));
-}
-
-// WaveSlot (lzq_quad.h) extended by the point's window.
-struct WinWaveSlot {
-  QuadSetup s;
-  EpiPre e;
-#if LZQ_ACC_LDS
-  double acc[kWaveSize];
-#endif
-  WinParams win;
-};
-
-struct SlotWindow {
-  static __device__ __forceinline__ double eval(const WinWaveSlot& slot, double y) {
-    return window_W(slot.win, __builtin_amdgcn_readfirstlane(slot.win.kind), y);
-  }
-};
-
-__device__ __forceinline__ void park_window(WinWaveSlot& slot, const QuadSetup& s, const EpiPre& e,
-                                            const WinParams& win, int lane) {
-  if (lane == 0) {
-    slot.s = s;
-    slot.e = e;
-    slot.win = win;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 
 // lzq_yields_batch_window: yields_points_kernel (lzq_kernels.hip) with the window of win[idx]
 template <int YB, int EXPV, int NZ>
@@ -147,14 +112,6 @@ __global__ __launch_bounds__(kBlock, LZQ_MIN_WAVES) void yields_grid_window_kern
   double Y_B;
   [[clang::always_inline]] Y_B = yb_wave<YB, EXPV, kYbDense, NZ, SlotWindow>(slots, w, zt, nzp, tab, truncate);
   if (lane == 0) out[local] = epilogue_finish(slots[w].e, Y_B);
-}
-
-// a grid point's z-sum table (lzq_kernels.hip table_of: the table axes' coordinates by tstride;
-// window axes lie between them with tstride 0)
-__device__ __forceinline__ int64_t win_table_of(const GridSpec& g, int64_t idx) {
-  int64_t t = 0;
-  for (int a = 0; a < g.n_axes; ++a) t += ((idx / g.stride[a]) % g.n[a]) * g.tstride[a];
-  return t;
 }
 
 // lzq_sweep_grid_from_ztables_window: points_reuse_window_kernel with the point, its block and its

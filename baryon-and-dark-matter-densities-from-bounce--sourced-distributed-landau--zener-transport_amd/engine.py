@@ -13,7 +13,7 @@ import torch
 
 import logging
 
-from . import _native, fit as _fit, window as _window
+from . import _native, fit as _fit, solve as _solve, window as _window
 from .config import to_aov, to_ctypes_aov, to_ctypes_ode, to_ctypes_point, to_point
 
 _log = logging.getLogger("lzq")
@@ -259,7 +259,7 @@ class Engine:
     def sweep(self, base_cfg, axes: Sequence[tuple], start: int, count: int, n_y: int = 8000,
               out: Optional[torch.Tensor] = None, P: Optional[float] = None,
               P_points: Optional[torch.Tensor] = None, reuse: bool = False, nz: int = _native.LZQ_NZ,
-              z_max: float = _native.LZQ_Z_MAX, window=None, window_tables=None) -> torch.Tensor:
+              z_max: float = _native.LZQ_Z_MAX, window=None, window_tables=None, solve=None):
         """axes: sequence of (field_name, values) (C order, last fastest); field names are
         the lzq_point double fields or 'delta_LZ' / 'm_mix' / 'dprime'.  P_points: optional
         per-point P override ([count], device), e.g. from lz_propagate (config C5).
@@ -274,10 +274,22 @@ class Engine:
         shared-z-sum twins; the z-sums do not depend on the window, so `reuse` applies as without one).
         Host axis values are checked before any upload (window.grid_check; LzqError names the axis and
         the value); values given as device tensors are not, and a block that cannot be evaluated then
-        gives NaN yields.  window_tables: the tabulated profiles of the table kind, as for yields."""
+        gives NaN yields.  window_tables: the tabulated profiles of the table kind, as for yields.
+        solve: the inverse sweep (lzq_sweep_grid_solve; see solve.py for the mapping): for every point the
+        value of one parameter in [lo, hi] at which a yield field takes a target value, found by a
+        bracketing root solve on the device.  Returns (records, results): the (count, 6) yield records at
+        the solutions and the (count, 6) results in _native.SOLVE_RESULT_FIELDS order.  Always through the
+        shared z-sum tables, built once per sweep as with `reuse`; tables beyond REUSE_MAX_BYTES raise
+        (there is no dense solve).  Every host-side refusal raises ValueError before any upload."""
         nz, z_max = _native.zgrid(nz, z_max)
         if len(axes) > _native.LZQ_MAX_AXES:
             raise ValueError(f"at most {_native.LZQ_MAX_AXES} sweep axes")
+        sv = None
+        if solve is not None:
+            if P_points is not None and _solve.normalize(solve)["field"] in ("P_chi_to_B", "delta_LZ", "m_mix", "dprime"):
+                raise ValueError("solve: a per-point P override (P_points) together with a solve for P or an LZ field")
+            sv = _solve.to_ctypes(_solve.check(solve, [n for n, _ in axes], window, self.lib))
+            reuse = True
         win = d_wt = None
         if window is not None:
             d_wt = self.window_tables_to_device(window_tables)
@@ -321,7 +333,9 @@ class Engine:
                                            for (n, v), t in zip(axes, dev_vals)), int(n_y), self._exp_variant, nz, z_max)
                 built = tkey == self._ztab_key
                 why = None if need * 8 <= REUSE_MAX_BYTES else f"{n_tables} z-sum tables exceed REUSE_MAX_BYTES"
-                if why is None and not built and not 0 < n_tables <= count:
+                if why is not None and sv is not None:
+                    raise ValueError(f"solve: {why}; the solve runs from the shared tables only")
+                if why is None and not built and not 0 < n_tables <= count and sv is None:
                     why = f"{n_tables} z-sum tables for a chunk of {count} points"
                 if why:
                     _log.warning("lzq reuse_zsums: dense path (same bits): %s", why)
@@ -334,9 +348,26 @@ class Engine:
                     if self._zwork is None or self._zwork.numel() < need:
                         self._zwork = torch.empty(max(int(need), 1), dtype=torch.float64, device=self.device)
                     ztables = self.lib.lzq_sweep_grid_ztables if win is None else self.lib.lzq_sweep_grid_ztables_window
-                    self._check(ztables(ctypes.byref(base), arr, len(axes), int(n_y), nz, z_max, _vp(self._zwork),
+                    t_arr, t_n = arr, len(axes)
+                    if sv is not None and sv.field in (_native.FIELD["m_mix"], _native.FIELD["dprime"]):
+                        # the solve stands for one of m_mix / dprime, which the table half refuses to see
+                        # alone; LZ axes contribute no table, so the list without them gives the same workspace
+                        keep = [a for a, (n, _) in enumerate(axes) if n not in ("m_mix", "dprime", "delta_LZ")]
+                        t_arr, t_n = (_native.LzqAxis * max(1, len(keep)))(), len(keep)
+                        for k, a in enumerate(keep):
+                            t_arr[k].field, t_arr[k].n, t_arr[k].values = arr[a].field, arr[a].n, arr[a].values
+                    self._check(ztables(ctypes.byref(base), t_arr, t_n, int(n_y), nz, z_max, _vp(self._zwork),
                                         self._zwork.numel(), self._stream()))
                     self._ztab_key = tkey
+                if sv is not None:
+                    sol = torch.empty((count, 6), dtype=torch.float64, device=self.device)
+                    self._check(self.lib.lzq_sweep_grid_solve(
+                        ctypes.byref(base), ctypes.byref(win) if win is not None else None, arr, len(axes),
+                        ctypes.byref(sv), int(start), int(count), int(n_y), nz, z_max, _vp(Pp), _vp(self._zwork),
+                        self._zwork.numel(), d_wt.arg if d_wt is not None else None, _vp(out), _vp(sol),
+                        self._stream()))
+                    self._keepalive = (dev_vals, d_wt)
+                    return out, sol
                 if win is None:
                     self._check(self.lib.lzq_sweep_grid_from_ztables(
                         ctypes.byref(base), arr, len(axes), int(start), int(count), int(n_y), nz, z_max, _vp(Pp),
@@ -354,6 +385,14 @@ class Engine:
                                                              d_wt.arg, _vp(out), self._stream()))
         self._keepalive = (dev_vals, d_wt)  # axis buffers (and window tables) must outlive the async launch
         return out
+
+    def solve_point(self, cfg, solve, window=None, window_tables=None, n_y: int = 8000, P: Optional[float] = None,
+                    nz: int = _native.LZQ_NZ, z_max: float = _native.LZQ_Z_MAX):
+        """The solve of one configuration: sweep(..., solve=solve) on a grid with no axes.  Returns
+        (record, result), two float64[6] device tensors."""
+        rec, sol = self.sweep(cfg, [], 0, 1, n_y=n_y, P=P, nz=nz, z_max=z_max, window=window,
+                              window_tables=window_tables, solve=solve)
+        return rec[0], sol[0]
 
     # -- sweep fits, posteriors, observables, ranked points (lzq_fit_*, lzq_post_*, lzq_obs_*,
     # lzq_rank_*): forwards to the device-resident states below; fit.py holds the specs and the

@@ -49,7 +49,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _native
+from . import _native, solve as _solve
 from .config import to_ode_params, to_point
 
 YIELD_FIELDS = _native.YIELD_FIELDS
@@ -187,6 +187,9 @@ class SweepSpec:
     # None = no cap (every window the reference accepts, as the single-point CLI does).
     ode_max_steps: Optional[int] = ODE_MAX_STEPS
     window: Optional[WindowSpec] = None   # None: the reference's window (fpy:262)
+    # the inverse sweep (solve.py): one parameter per grid point solved for a target yield; the table
+    # then holds the records at the solutions and solve.npy the results
+    solve: Optional[dict] = None
 
     @property
     def total(self) -> int:
@@ -218,6 +221,8 @@ class SweepSpec:
             d["ode_max_steps"] = self.ode_max_steps
         if self.window is not None:
             d["window"] = self.window.to_json()
+        if self.solve is not None:
+            d["solve"] = _solve.normalize(self.solve)
         return d
 
     def axis_values(self, start: int, count: int, device) -> dict:
@@ -365,9 +370,31 @@ def spec_from_json(d: dict) -> SweepSpec:
         raise ValueError("ode_max_steps must be >= 0 (0 or null: no cap)")
     # 0 means "no cap", as --ode-max-steps 0 on the command line does (one meaning in both places)
     spec = SweepSpec(d.get("name", "custom"), base, axes, int(d.get("n_y", 8000)), d.get("notes", ""), cr, method, prof,
-                     nz, z_max, None if ms is None or int(ms) == 0 else int(ms), win)
+                     nz, z_max, None if ms is None or int(ms) == 0 else int(ms), win,
+                     _solve.normalize(d["solve"]) if d.get("solve") else None)
     check_window_spec(spec)
+    check_solve_spec(spec)
     return spec
+
+
+def check_solve_spec(spec: SweepSpec) -> None:
+    """A "solve" section the sweep cannot run, as a ValueError that says why (before any upload): the
+    solve's own refusals (solve.check: the library's host-side checks), a spec whose points take the ODE
+    fallback, and a spec on the record path -- crossings or a profile P next to a solve for P or an LZ
+    field, or window axes that collide."""
+    if spec.solve is None:
+        return
+    sv = _solve.normalize(spec.solve)
+    if is_ode_spec(spec):
+        raise ValueError("a 'solve' section on a spec whose points take the ODE fallback (sigma_v / Gamma_wash / "
+                         "depletion): the solve stays in the quadrature regime")
+    if (spec.crossings is not None or spec.profile is not None) and \
+            sv["field"] in ("P_chi_to_B", "delta_LZ", "m_mix", "dprime"):
+        raise ValueError(f"solve for {sv['field']!r} on a spec whose P comes from crossings or a profile (a per-point "
+                         "P override)")
+    if spec.window is not None and window_axes_collide(spec):
+        raise ValueError("a 'solve' section on a spec whose window axes collide (the grid entry points refuse them)")
+    _solve.check(sv, [n for n, _ in grid_axes_for_kernel(spec)], None if spec.window is None else spec.window.block)
 
 
 def check_window_spec(spec: SweepSpec) -> None:
@@ -461,6 +488,11 @@ def _status_file(shard_path: str) -> str:
     return shard_path[:-len(".npy")] + ".status.npy"
 
 
+def _solve_file(shard_path: str) -> str:
+    """The solve results of one checkpointed chunk ((n, 6) float64), beside its records."""
+    return shard_path[:-len(".npy")] + ".solve.npy"
+
+
 def _save_shard(path: str, arr: np.ndarray) -> None:
     tmp = path + ".tmp.npy"
     np.save(tmp, arr, allow_pickle=False)
@@ -495,6 +527,18 @@ def run_local(compute: ComputeFn, start: int, end: int, make_out: Callable[[int]
         local = make_out(2 * n_ring)
     else:
         local = make_out(end - start)
+    # a solving compute (make_compute with a "solve" section) passes each chunk's (n, 6) results back
+    # on itself, as the ODE status counts travel: .solve_last after a call; the shard's results are
+    # collected here into .solve_local, each checkpointed chunk writing a .solve.npy sibling
+    solving = getattr(compute, "solve", None) is not None
+    # keep_table=False: no result table either -- the x column alone (NaN where a row has no solution)
+    # and integer counts, which is all the summary block needs (solve_summary_streamed)
+    if solving and keep_table:
+        compute.solve_local = make_out(end - start)
+    elif solving:
+        compute.solve_local = None
+        compute.solve_x = local.new_empty(end - start)
+        compute.solve_parts = torch.zeros(7, dtype=torch.int64, device=local.device)  # status counts, evals sum, max
     on_gpu = bool(getattr(local, "is_cuda", False)) and out_dir is not None
     pending = []    # (future, pinned buffer) of the writes in flight, oldest first
     ring = []       # pinned host buffers free for reuse
@@ -529,11 +573,29 @@ def run_local(compute: ComputeFn, start: int, end: int, make_out: Callable[[int]
                     if not os.path.exists(st):
                         raise RuntimeError(f"checkpoint {path} has no ODE status record {st}")
                     counts += np.load(st, allow_pickle=False)
+                if solving:
+                    sp = _solve_file(path)
+                    if not os.path.exists(sp):
+                        raise RuntimeError(f"checkpoint {path} has no solve record {sp}")
+                    sarr = np.load(sp, allow_pickle=False)
+                    if sarr.shape != (n, 6):
+                        raise RuntimeError(f"checkpoint {sp} has shape {sarr.shape}, expected {(n, 6)}")
+                    compute.solve_local[c0 - start:c0 - start + n].copy_(torch.from_numpy(sarr))
                 if fit is not None:
                     fit.update(view, c0)
                 log(f"resumed {path}")
                 continue
             compute(c0, n, view)
+            if solving and keep_table:
+                compute.solve_local[c0 - start:c0 - start + n].copy_(compute.solve_last)
+            elif solving:
+                r = compute.solve_last
+                status, ev = r[:, 5].to(torch.int64), r[:, 4].to(torch.int64)
+                compute.solve_x[c0 - start:c0 - start + n] = torch.where(status <= _native.SOLVE_MAX_EVALS, r[:, 0],
+                                                                         torch.full_like(r[:, 0], float("nan")))
+                compute.solve_parts[:5] += torch.bincount(status.clamp(0, 4), minlength=5)
+                compute.solve_parts[5] += ev.sum()
+                compute.solve_parts[6] = torch.maximum(compute.solve_parts[6], ev.max())
             if fit is not None:
                 fit.update(view, c0)
             log(f"chunk [{c0}, {c0 + n}) launched")
@@ -541,6 +603,9 @@ def run_local(compute: ComputeFn, start: int, end: int, make_out: Callable[[int]
                 continue
             if getattr(compute, "ode_status", None) is not None:
                 _save_shard(_status_file(path), np.asarray(compute.last_chunk, dtype=np.int64))
+            if solving:   # (written before the records: a table shard never stands without its sibling)
+                sync()
+                _save_shard(_solve_file(path), compute.solve_last.detach().cpu().numpy())
             if not on_gpu:
                 sync()
                 _save_shard(path, view.detach().cpu().numpy())
@@ -577,6 +642,32 @@ def run_local(compute: ComputeFn, start: int, end: int, make_out: Callable[[int]
         if on_gpu:
             pool.shutdown(wait=True)
     return local if keep_table else None
+
+
+def solve_summary_streamed(compute, total: int, rank: int, world: int, group=None) -> dict:
+    """The "solve" block of a keep_table=False sweep, the same on every rank and for every world size:
+    the ranks' integer counts are summed (the evaluations' maximum taken), and their x columns --
+    shards differ by at most one row, so each is padded to the longest with NaN -- gathered in one
+    collective (8 B a point: the one thing of a fit-only solve that grows with the grid)."""
+    import torch
+    import torch.distributed as dist
+    parts, x = compute.solve_parts.clone(), compute.solve_x
+    if dist.is_available() and dist.is_initialized():
+        nccl = dist.get_backend(group) == "nccl"
+        if not nccl:
+            parts, x = parts.cpu(), x.cpu()
+        mx = parts[6:7].clone()
+        dist.all_reduce(parts, group=group)
+        dist.all_reduce(mx, op=dist.ReduceOp.MAX, group=group)
+        parts[6] = mx[0]
+        m = max(e - b for b, e in (shard_range(total, r, world) for r in range(world)))
+        pad = torch.full((m,), float("nan"), dtype=x.dtype, device=x.device)
+        pad[:x.numel()] = x
+        allx = torch.empty(world * m, dtype=x.dtype, device=x.device)
+        dist.all_gather_into_tensor(allx, pad, group=group)
+        x = allx
+    parts = parts.cpu().numpy()
+    return _solve.summary_from_parts(compute.solve, x.cpu().numpy(), parts[:5], int(parts[5]), int(parts[6]), total)
 
 
 def launched_distributed(world: int) -> bool:
@@ -702,6 +793,13 @@ def run_sweep(spec: SweepSpec, engine=None, rank: int = 0, world: int = 1, chunk
                       out_dir, resume, sync=torch.cuda.synchronize, log=log, key=key, fit=acc,
                       keep_table=keep_table)
     run_sweep.ode_status = ode_status_summary(getattr(compute, "ode_status", None), group, engine.device)
+    # the solve results: six doubles a row, gathered like the records (the same on every rank)
+    solving = getattr(compute, "solve", None) is not None
+    run_sweep.solve = gather_table(compute.solve_local, spec.total, rank, world, group) \
+        if solving and keep_table else None
+    run_sweep.solve_summary = None if not solving else (
+        _solve.summary(compute.solve, run_sweep.solve.cpu().numpy()) if keep_table
+        else solve_summary_streamed(compute, spec.total, rank, world, group))
     table = gather_table(local, spec.total, rank, world, group) if keep_table else None
     if acc is None:
         return table
@@ -777,6 +875,23 @@ def make_compute(spec: SweepSpec, engine, reuse: bool = False, window_host_recor
     entry points would take it (the same bits; tools/bench_window.py's baseline)."""
     pcache = {}   # the profile's device splines, built once per sweep
     check_window_spec(spec)
+    check_solve_spec(spec)
+    if spec.solve is not None:
+        # the inverse sweep: always from the shared z-sum tables (Engine.sweep(solve=)); the records at
+        # the solutions go to `out`, the results ride back on the function (run_local collects them)
+        d_tables = engine.window_tables_to_device(spec.window.host_tables()) if spec.window is not None else None
+
+        def compute_solve(s, n, out):
+            P_points = coherent_P(spec, s, n, engine) if spec.crossings is not None else None
+            if spec.profile is not None:
+                P_points = profile_P(spec, s, n, engine, pcache)
+            _, compute_solve.solve_last = engine.sweep(
+                spec.base, grid_axes_for_kernel(spec), s, n, n_y=spec.n_y, out=out, P_points=P_points, nz=spec.nz,
+                z_max=spec.z_max, window=None if spec.window is None else spec.window.block, window_tables=d_tables,
+                solve=spec.solve)
+        compute_solve.solve = _solve.normalize(spec.solve)
+        compute_solve.solve_last = compute_solve.solve_local = None
+        return compute_solve
     if spec.window is not None:
         d_tables = engine.window_tables_to_device(spec.window.host_tables())
         grid_regime = int(to_point(spec.base)["regime"][0]) in (_native.THERMAL, _native.NONTHERMAL)
@@ -881,6 +996,12 @@ def main(argv=None):
                          "fit.json, fit_maps.npz, selected.npy, with \"observables\" (histograms over yield fields) "
                          "fit_obs.npz, with \"ranked\" (the n best points with their records) fit_ranked.npz, and a "
                          "\"fit\" block in summary.json")
+    ap.add_argument("--solve", default=None, metavar="FIELD:LO:HI[:TARGETFIELD=VALUE]",
+                    help="the inverse sweep: for every grid point solve FIELD in [LO, HI] for a target yield "
+                         "(default DM_over_B=5.357), e.g. --spec C3 --solve source_shape_sigma_y:1:50; table.npy then "
+                         "holds the records at the solutions, solve.npy (x, x_lo, x_hi, residual, evals, status) the "
+                         "results, and summary.json a \"solve\" block (with --no-table only the block).  Replaces a spec file's "
+                         "\"solve\" section")
     ap.add_argument("--no-table", action="store_true",
                     help="with --fit: keep only the fit -- chunks pass through two chunk-sized buffers, there is "
                          "no all-gather, no table.npy and no checkpoint (a grid larger than HBM or the disk)")
@@ -901,6 +1022,10 @@ def main(argv=None):
                                             spec.z_max if args.z_max is None else args.z_max)
     if args.ode_max_steps is not None:
         spec.ode_max_steps = None if args.ode_max_steps == 0 else args.ode_max_steps
+    if args.solve is not None:
+        spec.solve = _solve.parse_cli(args.solve)
+    if spec.solve is not None:
+        check_solve_spec(spec)
     fitspec = fit_maps = None
     if args.fit is not None:
         from . import fit as _fit
@@ -936,6 +1061,11 @@ def main(argv=None):
                       keep_table=not args.no_table)
     ode_status = ode_status_summary(getattr(compute, "ode_status", None), None, eng.device)
     table = None if args.no_table else gather_table(local, spec_total, rank, world)
+    solved = gather_table(compute.solve_local, spec_total, rank, world) \
+        if spec.solve is not None and not args.no_table else None
+    # --no-table: no solve.npy either; the summary block from the x column and integer counts
+    solve_block = solve_summary_streamed(compute, spec_total, rank, world) \
+        if spec.solve is not None and args.no_table else None
     fit_result = _fit.combine(acc, world, local=local, start=start) if acc is not None else None
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
@@ -956,6 +1086,13 @@ def main(argv=None):
                     "per_point" if t["per_point_chunks"] == t["chunks"] else "mixed"))
         if args.reuse_zsums:
             summ["reuse_zsums"] = eng.last_reuse
+        if solve_block is not None:
+            summ["solve"] = solve_block
+        if solved is not None:
+            sol = solved.cpu().numpy()
+            summ["solve"] = _solve.summary(spec.solve, sol)
+            if args.out:
+                np.save(os.path.join(args.out, "solve.npy"), sol, allow_pickle=False)
         if fit_result is not None:
             best = fit_result["best"]["index"]
             fit_rep = _fit.report(fitspec, fit_result, spec, spec_total,

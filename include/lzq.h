@@ -359,6 +359,66 @@ int lzq_window_grid_blocks_host(const lzq_window* base_win, const lzq_axis* axes
  * message names the axis (its position in axes) and the value. */
 int lzq_window_grid_check_host(const lzq_window* base_win, const lzq_axis* axes, int32_t n_axes,
                                const lzq_window_tables* host_tables);
+/* ---- one parameter per grid point solved for a target yield (PAPER eqs.(22)-(24), §10) ---- */
+/* The inverse of a sweep: for every point of a grid, the value x of ONE parameter in [lo, hi] at
+ * which a yield field takes a target value (e.g. the P_eff at which DM_over_B = 5.357, PAPER
+ * eq.(24)), found on the device by a bracketing root solve of f(x) = field(x) - target (one IEEE
+ * subtraction).  csrc/lzq_solve.h holds the stepping rule, one definition that the host and the
+ * device build: f(lo), then f(hi); then regula-falsi points (a fb - b fa)/(fb - fa) with the
+ * Anderson-Bjorck scaling of a twice-retained end's f, replaced by the midpoint a + (b - a)/2 when
+ * they do not fall strictly inside the bracket or when the width would otherwise not have halved
+ * over three evaluations.  Guarantees: the bracket [x_lo, x_hi]
+ * keeps a strict sign change of f; its width at least halves every three evaluations; evals <=
+ * max_evals (clamped to [2, 256] on the host and again in the kernel); the result is a pure function
+ * of (point, block, solve), independent of the range, chunk or shard it is computed in.  The solve
+ * stops when x_hi - x_lo <= xtol max(|x_lo|, |x_hi|), when no double lies strictly between the
+ * ends, at an exact zero of f (then x_lo = x = x_hi), or after max_evals evaluations
+ * (LZQ_SOLVE_MAX_EVALS: the bracket is still valid and returned).  x is the end with the smaller
+ * |f| (ties: the lower one), residual = f(x) as evaluated there.
+ *
+ * Allowed solve fields are those that contribute no z-sum table, so that every evaluation is one
+ * point integrated from the grid's shared tables: m_chi, g_chi, v_w, g_star, g_star_s, P, sigma_y,
+ * flux, Y_chi_init, n_chi_at_Tp; the LZ fields delta_LZ, m_mix, dprime (the other one of m_mix /
+ * dprime must then be an axis; a solve for v_w on a grid with m_mix / dprime axes re-forms their P
+ * with v_w = x, PAPER eq.(8), as the forward sweep does with v_w as an axis); with a block,
+ * LZQ_F_WIN_Y0, _HALF_WIDTH, _SIGMA_LO, _SIGMA_HI, _SIGMA, _SCALE.  LZQ_EINVAL with a message
+ * (lzq_solve_check_host: the same checks without a GPU) for: a table field (I_p, beta_over_H, T_p, T_min / T_max_over_Tp); LZQ_F_WIN_TABLE; a window field
+ * without a block; sigma_y with a block (the block replaces it); a field that an axis also writes
+ * (for window fields: whose masks meet, as for two axes; P counts as written by every LZ axis, delta_LZ by m_mix / dprime axes); lo >= hi or
+ * non-finite bounds or target; xtol outside [0, 1); target_field outside [0, 5]; d_P together with a
+ * solve for P or an LZ field.
+ *
+ * d_work: the tables of lzq_sweep_grid_ztables (base_win NULL) or lzq_sweep_grid_ztables_window for
+ * the same base, axes and n_y; the solve builds none.  (For a solve of m_mix or dprime the axis list
+ * holds the other one alone, which the table entry points refuse: build the tables from the list
+ * without its LZ axes -- they contribute no table, so the workspace is the same.)
+ * d_out[i]: the yield record at x, the
+ * evaluation's own -- bit for bit what lzq_sweep_grid_from_ztables[_window] returns for that grid
+ * point with the solve field set to x.  d_sol[i]: six doubles, so a table of results travels like a
+ * table of records.  For LZQ_SOLVE_NO_BRACKET (f(lo) and f(hi) of one strict sign), LZQ_SOLVE_NAN (a
+ * non-finite f, at an end or inside; also a point whose decoded window block is a refusal, which
+ * reads no window table) and LZQ_SOLVE_BAD_TABLE (the table's header does not match the point's
+ * y-grid, c or z grid; tested once, at lo) all six yields, x and residual are NaN and x_lo, x_hi
+ * are the given bounds. */
+enum lzq_solve_status { LZQ_SOLVE_OK = 0, LZQ_SOLVE_MAX_EVALS = 1, LZQ_SOLVE_NO_BRACKET = 2,
+                        LZQ_SOLVE_NAN = 3, LZQ_SOLVE_BAD_TABLE = 4 };
+typedef struct lzq_solve {          /* host struct, 48 bytes */
+  int32_t field;        /* enum lzq_field: the parameter solved for */
+  int32_t target_field; /* 0..5: index into lzq_yield */
+  double lo, hi, target, xtol;
+  int32_t max_evals;    /* clamped to [2, 256] */
+} lzq_solve;
+typedef struct lzq_solve_result {   /* 48 bytes */
+  double x, x_lo, x_hi, residual, evals, status;
+} lzq_solve_result;
+int lzq_sweep_grid_solve(const lzq_point* base, const lzq_window* base_win /* NULL: the point's Gaussian */,
+                         const lzq_axis* axes, int32_t n_axes, const lzq_solve* solve, int64_t start, int64_t count,
+                         int32_t n_y, int32_t nz, double z_max, const double* d_P, const double* d_work,
+                         int64_t work_doubles, const lzq_window_tables* d_tables,
+                         lzq_yield* d_out, lzq_solve_result* d_sol, void* stream);
+/* The solve's host-side refusals (all of the above but d_P's).  Axis values are not read.  No GPU. */
+int lzq_solve_check_host(const lzq_solve* solve, const lzq_window* base_win, const lzq_axis* axes, int32_t n_axes);
+
 /* The ODE entry points below take no window: their source term keeps the reference's Gaussian
  * (fpy:226-228).  Engine.ode and the facade's ODE operators raise when given another one. */
 
