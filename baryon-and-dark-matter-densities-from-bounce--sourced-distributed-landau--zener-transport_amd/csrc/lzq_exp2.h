@@ -273,6 +273,11 @@ LZQ_HD double exp2_tab_scaled(double c2N, double g, const double* tabp) {
 // Both tests evaluate the loop's own expression, so they are exact.  When every lane of a wave
 // passes one, the node's lookup (address, LDS read, exponent insert, and the max) returns the
 // value of the node before: seg_entry fetches it once, seg_node is the rest of the node.
+// On a zero stretch the range reduction is known as well: t_k = M at every node, so the node's
+// w = (M + A) - t_k is (M + A) - M = A exactly (both integers below 2^53), and s = fma(c2N, g, w)
+// is fma(c2N, g, A) -- seg_node_zero forms s from that operand directly and drops t and w; the
+// rest of the node (q, v) is seg_node's, so the bits are.  (The invariant is the zero test's:
+// t_k = M  =>  w = A.  It does not hold on the clamped stretch, whose unclamped t still moves.)
 constexpr double kTabMagic = 0x1.8p52;
 constexpr double kTabTClamp = kTabMagic + (double)kTabKMin;  // exact
 
@@ -293,6 +298,14 @@ LZQ_HD double seg_entry(const double* tabp, double tc) {
 LZQ_HD double seg_node(double c2N, double g, double Mv, double Ts) {
   const double t = __builtin_fma(c2N, g, Mv);
   const double s = __builtin_fma(c2N, g, (kTabMagic + kSqA) - t);  // the unclamped t, as in the general node
+  return Ts * __builtin_fma(s, s, kSqBeta);
+}
+
+// one node of a zero stretch (seg_zero held for this lane at g_max, 0 <= g <= g_max): seg_node with
+// t = M and w = A known, i.e. its s, q and v on the same operands.  (Av = kSqA: a parameter so that
+// the device can pin it in a VGPR, as Mv above.)
+LZQ_HD double seg_node_zero(double c2N, double g, double Av, double Ts) {
+  const double s = __builtin_fma(c2N, g, Av);
   return Ts * __builtin_fma(s, s, kSqBeta);
 }
 

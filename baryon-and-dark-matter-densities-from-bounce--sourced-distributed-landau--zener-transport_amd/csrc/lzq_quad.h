@@ -67,6 +67,12 @@ constexpr int kWavesPerBlock = kBlock / kWaveSize;
 #ifndef LZQ_UNIFORM_SEG
 #define LZQ_UNIFORM_SEG 1
 #endif
+// the whole-pass zero stretch (every lane has round(u) = 0 at every node) also runs without the
+// range reduction, whose results the pass test has already fixed: t = M, w = A (seg_node_zero in
+// lzq_exp2.h; four FP64 operations per node instead of six); 0: the six-operation uniform node
+#ifndef LZQ_ZERO_SEG
+#define LZQ_ZERO_SEG 1
+#endif
 constexpr int kKUnroll = LZQ_KUNROLL;  // z-nodes per scalar-load batch (must divide 1200)
 constexpr int kYB = LZQ_YB;            // y-nodes per lane per pass (independent chains)
 static_assert(kNZ % kKUnroll == 0, "z unroll must divide nz");
@@ -348,9 +354,13 @@ __device__ __forceinline__ double c2_scale() { return EXPV == kExpTable ? (doubl
 // the lookup (address, ds_read, insert, and the max) returns what it returned at the node before.
 // zsum_dispatch finds those stretches per pass with the loop's own t and runs them through
 // zsum_uniform below: the same six FP64 operations per node on the same operands, the entry fetched
-// once (LZQ_UNIFORM_SEG; 80.3% of the C2 workload's nodes, tools/uniform_segment_share.py).  No
-// node is skipped and the bits are the general loop's (tests/test_zsum_segments_host.py,
-// tests/test_gpu_zsum_segments.py).
+// once (LZQ_UNIFORM_SEG; 80.3% of the C2 workload's nodes, tools/uniform_segment_share.py).  On the
+// first kind of stretch (t = M at every node, 64.0% of the nodes) two of the six are known before
+// the loop starts -- t = M, and w = (M + A) - M = A exactly -- and the node runs the other four:
+// s = fma(c2, g, A), q, v and F's fma, on the operands the six-operation node hands them
+// (LZQ_ZERO_SEG).  No node is skipped and the bits are the general loop's
+// (tests/test_zsum_segments_host.py, tests/test_zsum_zero_segment_host.py,
+// tests/test_gpu_zsum_segments.py, tests/test_gpu_zsum_zero_segment.py).
 template <int YB, int EXPV, bool CLAMP = true>
 __device__ __forceinline__ void zsum(const ZNode* __restrict__ zt, const double* tab, const double (&c2)[YB],
                                      double (&F)[YB], int kend, int kbeg = 0) {
@@ -432,14 +442,20 @@ __device__ __forceinline__ void zsum(const ZNode* __restrict__ zt, const double*
 // operations on the same operands in the same order (seg_node: t, w, s, q, v, and F's fma) --
 // no max, no address, no ds_read, no insert.  Every node is executed; F carries on from kbeg in
 // node order like the general loop's.
-template <int YB>
+//
+// ZERO (LZQ_ZERO_SEG; the caller has shown t = M for every lane at g_max, hence at every node):
+// t and w are not recomputed -- w is A exactly, so s = fma(c2, g, A) is the same instruction on the
+// same operand (seg_node_zero) -- and a node is four FP64 operations: s, q, v, and F's fma.  A takes
+// the loop's one pinned VGPR pair, where M sits otherwise: g, beta, Ts and omega' are scalar
+// operands already and a VOP3 instruction reads one, so a scalar A would cost a v_mov per node.
+template <int YB, bool ZERO = false>
 __device__ __forceinline__ void zsum_uniform(const ZNode* __restrict__ zt, double Ts, const double (&c2)[YB],
                                              double (&F)[YB], int kend, int kbeg) {
   if (kbeg == 0) {
 #pragma unroll
     for (int b = 0; b < YB; ++b) F[b] = 0.0;
   }
-  const double Mv = vgpr_const(kTabMagic);
+  const double Pv = vgpr_const(ZERO ? kSqA : kTabMagic);  // the pinned pair: A, or M
   for (int k = kbeg; k < kend; k += kKUnroll) {
     double g4[kKUnroll], om[kKUnroll];
 #pragma unroll
@@ -450,7 +466,10 @@ __device__ __forceinline__ void zsum_uniform(const ZNode* __restrict__ zt, doubl
 #pragma unroll
     for (int kk = 0; kk < kKUnroll; ++kk)
 #pragma unroll
-      for (int b = 0; b < YB; ++b) F[b] = __builtin_fma(om[kk], seg_node(c2[b], g4[kk], Mv, Ts), F[b]);
+      for (int b = 0; b < YB; ++b) {
+        const double v = ZERO ? seg_node_zero(c2[b], g4[kk], Pv, Ts) : seg_node(c2[b], g4[kk], Pv, Ts);
+        F[b] = __builtin_fma(om[kk], v, F[b]);
+      }
   }
 }
 
@@ -515,8 +534,9 @@ __device__ __forceinline__ void zsum_dispatch(const ZNode* __restrict__ zt, int 
   }
   if constexpr (EXPV == kExpTable && kSqForm && LZQ_UNIFORM_SEG) {
     // Uniform-entry segments, decided per pass with the loop's own t = fma(c2, g, M) (lzq_exp2.h):
-    //   every lane has t = M at g_max (small |c2|, or dead: c2e = 0): t = M at every node, the
-    //     whole pass reads T''[0] with nothing inserted;
+    //   every lane has t = M at g_max (small |c2|, or dead: c2e = 0): t = M at every node (g4 runs
+    //     from >= 0 up to g_max, padding nodes repeat g_max), the whole pass reads T''[0] with
+    //     nothing inserted and, with LZQ_ZERO_SEG, forms s from w = A without recomputing t;
     //   else, on a pass that can clamp: from the first batch k2 at whose first node every lane
     //     has t <= M + KMIN, every lane reads the entry of M + KMIN (t only falls with k); the
     //     nodes before k2 run the clamped general loop.  A wave-uniform binary search.
@@ -525,7 +545,7 @@ __device__ __forceinline__ void zsum_dispatch(const ZNode* __restrict__ zt, int 
 #pragma unroll
     for (int b = 0; b < YB; ++b) zero = zero && seg_zero(c2e[b], g_max, Mv);
     if (__all(zero)) {
-      zsum_uniform<YB>(zt, uniform(seg_entry(tab, kTabMagic)), c2e, F, kend, 0);
+      zsum_uniform<YB, LZQ_ZERO_SEG != 0>(zt, uniform(seg_entry(tab, kTabMagic)), c2e, F, kend, 0);
     } else if (__all(small)) {
       zsum<YB, EXPV, false>(zt, tab, c2e, F, kend);
     } else {

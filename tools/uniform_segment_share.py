@@ -8,6 +8,11 @@ batch search of csrc/lzq_exp2.h that the device's zsum_dispatch calls (c2 with n
 from the device's exp_sc: a pass whose boundary lane sits within 1e-16 of a predicate's threshold
 could be planned differently, by one 8-node batch of 150,000).
 
+Also printed: the share of nodes in whole-uniform (zero) passes, which run without the range
+reduction (LZQ_ZERO_SEG, zsum_uniform<YB, true>), and the VALU instructions per wave-node that share
+predicts from the parent build's PMC (profiles/round8/parent_pmc_summary.json), to set beside the
+shipped kernel's PMC (profiles/round6/pmc_summary.json).
+
     python tools/uniform_segment_share.py
 """
 import json
@@ -35,13 +40,24 @@ def main():
     zero = int(kend[path == H.ZERO].sum())
     suffix = int((kend - k2)[path == H.SPLIT].sum())
     split = path == H.SPLIT
+    # LZQ_ZERO_SEG: a node of a whole-uniform (zero) pass runs without t and w, an FMA and an ADD fewer
+    # on every node of those passes; set beside the PMC of profiles/round8/parent_pmc_summary.json
+    # (the six-operation node everywhere) this predicts the VALU per wave-node of the shipped kernel
+    with open(os.path.join(ROOT, "profiles", "round8", "parent_pmc_summary.json")) as f:
+        parent = json.load(f)
+    mix = dict(parent["valu_mix_per_wave_node"])
+    mix["fma_f64"] -= zero / nodes
+    mix["add_f64"] -= zero / nodes
     print(json.dumps({
         "passes": int(len(path)), "nodes_per_point": nodes,
         "passes_whole_uniform": int((path == H.ZERO).sum()), "passes_clamp_free": int((path == H.FREE).sum()),
         "passes_clamped": int(split.sum()), "clamped_passes_with_suffix": int((split & (k2 < kend)).sum()),
         "k2_of_clamped_passes": k2[split].tolist(),
         "uniform_nodes_whole_pass": zero, "uniform_nodes_clamped_suffix": suffix,
-        "uniform_share": (zero + suffix) / nodes}))
+        "uniform_share": (zero + suffix) / nodes,
+        "zero_pass_share": zero / nodes,
+        "predicted_valu_per_wave_node": parent["valu_insts_per_wave_node"] - 2.0 * zero / nodes,
+        "predicted_valu_mix_per_wave_node": mix}))
 
 
 if __name__ == "__main__":
