@@ -278,6 +278,9 @@ LZQ_HD double exp2_tab_scaled(double c2N, double g, const double* tabp) {
 // is fma(c2N, g, A) -- seg_node_zero forms s from that operand directly and drops t and w; the
 // rest of the node (q, v) is seg_node's, so the bits are.  (The invariant is the zero test's:
 // t_k = M  =>  w = A.  It does not hold on the clamped stretch, whose unclamped t still moves.)
+// A dead lane runs the zero stretch with c2N = +0.0, and then s = fma(+0 * g, A) = A whatever g is:
+// q and v are fixed too, seg_node_dead forms them without c2N or g, and only F's accumulate is left
+// per node (lzq_quad.h runs it that way where all 64 lanes are dead).
 constexpr double kTabMagic = 0x1.8p52;
 constexpr double kTabTClamp = kTabMagic + (double)kTabKMin;  // exact
 
@@ -308,6 +311,15 @@ LZQ_HD double seg_node_zero(double c2N, double g, double Av, double Ts) {
   const double s = __builtin_fma(c2N, g, Av);
   return Ts * __builtin_fma(s, s, kSqBeta);
 }
+
+// one node of a zero stretch on a dead lane, whose c2N is the literal +0.0 (zsum_dispatch's c2e):
+// s = fma(+0 * g, A) is A exactly for every finite g >= 0, so the node is seg_node_zero(0.0, g, A, Ts)
+// whatever g is -- one value for the whole pass, formed once.  Only for that +0.0: a c2N of -0.0 or a
+// subnormal also leaves s = A, but the dispatch never hands one over as "dead", and any c2N whose
+// product with g can reach half an ulp of A does move s.  (Av = kSqA, as in seg_node_zero.  beta is
+// handed over as the fma's scalar operand: it is one already, in the loops of the other paths, and
+// a VGPR copy of it was kept live across the y-loop, at the cost of a spill.)
+LZQ_HD double seg_node_dead(double Av, double Ts) { return Ts * fma_vvs(Av, Av, kSqBeta); }
 
 // First node k2 in [0, kend], a multiple of `unroll` (which divides kend), with pred(g4(k2)); pred
 // must be monotone in k (false ... false true ... true); kend if it holds at no batch start.

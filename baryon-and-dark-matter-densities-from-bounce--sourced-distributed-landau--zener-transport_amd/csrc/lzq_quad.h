@@ -73,6 +73,13 @@ constexpr int kWavesPerBlock = kBlock / kWaveSize;
 #ifndef LZQ_ZERO_SEG
 #define LZQ_ZERO_SEG 1
 #endif
+// a whole-pass zero stretch whose 64 lanes are all dead (c2e = +0.0 in every lane) also forms the
+// node's value once per pass: s = fma(+0 * g, A) = A, so q and v are one number at every node and
+// only F's accumulate runs per node (seg_node_dead in lzq_exp2.h, zsum_dead; one FP64 operation per
+// node instead of four).  Needs LZQ_ZERO_SEG; 0: those passes run the four-operation zero node
+#ifndef LZQ_DEAD_SEG
+#define LZQ_DEAD_SEG 1
+#endif
 constexpr int kKUnroll = LZQ_KUNROLL;  // z-nodes per scalar-load batch (must divide 1200)
 constexpr int kYB = LZQ_YB;            // y-nodes per lane per pass (independent chains)
 static_assert(kNZ % kKUnroll == 0, "z unroll must divide nz");
@@ -358,9 +365,12 @@ __device__ __forceinline__ double c2_scale() { return EXPV == kExpTable ? (doubl
 // first kind of stretch (t = M at every node, 64.0% of the nodes) two of the six are known before
 // the loop starts -- t = M, and w = (M + A) - M = A exactly -- and the node runs the other four:
 // s = fma(c2, g, A), q, v and F's fma, on the operands the six-operation node hands them
-// (LZQ_ZERO_SEG).  No node is skipped and the bits are the general loop's
+// (LZQ_ZERO_SEG).  Where all 64 lanes of such a pass are dead (c2 = +0.0 in every lane, 24.8% of the
+// nodes) s = A as well, so q and v are one number for the pass and the node runs F's fma alone
+// (LZQ_DEAD_SEG, zsum_dead).  No node is skipped and the bits are the general loop's
 // (tests/test_zsum_segments_host.py, tests/test_zsum_zero_segment_host.py,
-// tests/test_gpu_zsum_segments.py, tests/test_gpu_zsum_zero_segment.py).
+// tests/test_zsum_dead_segment_host.py, tests/test_gpu_zsum_segments.py,
+// tests/test_gpu_zsum_zero_segment.py, tests/test_gpu_zsum_dead_segment.py).
 template <int YB, int EXPV, bool CLAMP = true>
 __device__ __forceinline__ void zsum(const ZNode* __restrict__ zt, const double* tab, const double (&c2)[YB],
                                      double (&F)[YB], int kend, int kbeg = 0) {
@@ -473,6 +483,28 @@ __device__ __forceinline__ void zsum_uniform(const ZNode* __restrict__ zt, doubl
   }
 }
 
+// The all-dead loop (LZQ_DEAD_SEG): a zero pass whose 64 lanes are all dead, so every lane runs with
+// c2e = +0.0.  Then s = fma(+0 * g, A) = A at every node, and q = fma(A, A, beta) and v = T''[0] * q
+// are the same two numbers at each of them (seg_node_dead): they are formed once, and a node is F's
+// accumulate alone, F = fma(omega'_k, v0, F), on the operands zsum_uniform<YB, true> hands it, in node
+// order from F = 0.  No node is skipped.  v0 takes the loop's one pinned VGPR pair; omega' is the
+// instruction's scalar operand, and g4 is not read.
+template <int YB>
+__device__ __forceinline__ void zsum_dead(const ZNode* __restrict__ zt, double Ts, double (&F)[YB], int kend) {
+#pragma unroll
+  for (int b = 0; b < YB; ++b) F[b] = 0.0;
+  const double v0 = seg_node_dead(vgpr_const(kSqA), Ts);
+  for (int k = 0; k < kend; k += kKUnroll) {
+    double om[kKUnroll];
+#pragma unroll
+    for (int kk = 0; kk < kKUnroll; ++kk) om[kk] = zt[k + kk].omega;
+#pragma unroll
+    for (int kk = 0; kk < kKUnroll; ++kk)
+#pragma unroll
+      for (int b = 0; b < YB; ++b) F[b] = __builtin_fma(om[kk], v0, F[b]);
+  }
+}
+
 // Pass-level wrapper: "dead" lanes, c2 * g4_1 <= -N*1077 (every node k >= 1 underflows to
 // exactly 0: g4 is increasing and omega_0 = 0), run the loop with c2 = 0 and are zeroed
 // afterwards -- the same instruction stream, the exact zero.
@@ -536,7 +568,8 @@ __device__ __forceinline__ void zsum_dispatch(const ZNode* __restrict__ zt, int 
     // Uniform-entry segments, decided per pass with the loop's own t = fma(c2, g, M) (lzq_exp2.h):
     //   every lane has t = M at g_max (small |c2|, or dead: c2e = 0): t = M at every node (g4 runs
     //     from >= 0 up to g_max, padding nodes repeat g_max), the whole pass reads T''[0] with
-    //     nothing inserted and, with LZQ_ZERO_SEG, forms s from w = A without recomputing t;
+    //     nothing inserted and, with LZQ_ZERO_SEG, forms s from w = A without recomputing t; if
+    //     every lane is dead as well (LZQ_DEAD_SEG), s = A too and the node is F's fma alone;
     //   else, on a pass that can clamp: from the first batch k2 at whose first node every lane
     //     has t <= M + KMIN, every lane reads the entry of M + KMIN (t only falls with k); the
     //     nodes before k2 run the clamped general loop.  A wave-uniform binary search.
@@ -544,7 +577,14 @@ __device__ __forceinline__ void zsum_dispatch(const ZNode* __restrict__ zt, int 
     bool zero = true;
 #pragma unroll
     for (int b = 0; b < YB; ++b) zero = zero && seg_zero(c2e[b], g_max, Mv);
-    if (__all(zero)) {
+    // every lane dead (tested first: dead lanes pass the zero test): the zero pass whose node value
+    // is fixed as well (zsum_dead); a pass holding one live lane takes the paths below
+    bool all_dead = LZQ_ZERO_SEG != 0 && LZQ_DEAD_SEG != 0;
+#pragma unroll
+    for (int b = 0; b < YB; ++b) all_dead = all_dead && dead[b];
+    if (LZQ_ZERO_SEG != 0 && LZQ_DEAD_SEG != 0 && __all(all_dead)) {
+      zsum_dead<YB>(zt, uniform(seg_entry(tab, kTabMagic)), F, kend);
+    } else if (__all(zero)) {
       zsum_uniform<YB, LZQ_ZERO_SEG != 0>(zt, uniform(seg_entry(tab, kTabMagic)), c2e, F, kend, 0);
     } else if (__all(small)) {
       zsum<YB, EXPV, false>(zt, tab, c2e, F, kend);

@@ -3,15 +3,18 @@
 (csrc/lzq_quad.h zsum_uniform, LZQ_UNIFORM_SEG) on the C2 workload, counted on the host.
 
 Every C2 point has the same y grid and the same c, so the 125 passes of one point are the whole
-grid.  The passes are planned by tests/zsum_segments_host.cpp, i.e. by the LZQ_HD predicates and
-batch search of csrc/lzq_exp2.h that the device's zsum_dispatch calls (c2 with numpy's exp, <= 1 ulp
-from the device's exp_sc: a pass whose boundary lane sits within 1e-16 of a predicate's threshold
-could be planned differently, by one 8-node batch of 150,000).
+grid.  The passes are planned by tests/zsum_dead_segment_host.cpp, i.e. by the LZQ_HD predicates and
+batch search of csrc/lzq_exp2.h that the device's zsum_dispatch calls, the dead rule among them (c2
+with numpy's exp, <= 1 ulp from the device's exp_sc: a pass whose boundary lane sits within 1e-16 of
+a predicate's threshold could be planned differently, by one 8-node batch of 150,000).
 
 Also printed: the share of nodes in whole-uniform (zero) passes, which run without the range
 reduction (LZQ_ZERO_SEG, zsum_uniform<YB, true>), and the VALU instructions per wave-node that share
-predicts from the parent build's PMC (profiles/round8/parent_pmc_summary.json), to set beside the
-shipped kernel's PMC (profiles/round6/pmc_summary.json).
+predicts from the PMC of the build without it (profiles/round8/parent_pmc_summary.json); and the
+all-dead passes among them, which form the node's value once (LZQ_DEAD_SEG, zsum_dead: F's fma alone
+per node, two FMA and one MUL fewer), with the VALU count and mix their share predicts from the PMC
+of the build without that (profiles/round9/parent_pmc_summary.json), to set beside the shipped
+kernel's PMC (profiles/round6/pmc_summary.json).
 
     python tools/uniform_segment_share.py
 """
@@ -23,8 +26,13 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
-import test_zsum_segments_host as H  # noqa: E402
-import zsum_ref as Z                  # noqa: E402
+import test_zsum_dead_segment_host as H  # noqa: E402
+import zsum_ref as Z                      # noqa: E402
+
+
+def _parent(rnd):
+    with open(os.path.join(ROOT, "profiles", rnd, "parent_pmc_summary.json")) as f:
+        return json.load(f)
 
 
 def main():
@@ -34,30 +42,46 @@ def main():
     g = Z.grid(1200, 30.0)
     c2 = ((-(I_p / 6.0) * np.exp(np.clip(ys, -50.0, 50.0))) * Z.LOG2E) * 8192.0
     c2 = np.concatenate([c2, np.full(-len(c2) % 64, c2[-1])])      # tail lanes recompute the last node
-    _, plan = H.run(H.load_lib(), g, c2, 1, 0)
+    L = H.load_lib()
+    _, _, plan = H.run(L, g, c2, H.DEADSEG, 0)
     path, k2, kend = plan[:, 0], plan[:, 1], plan[:, 2]
     nodes = int(kend.sum())
-    zero = int(kend[path == H.ZERO].sum())
+    dead = int(kend[path == H.DEAD].sum())
+    zero = int(kend[path == H.ZERO].sum()) + dead                  # the all-dead passes are zero passes
     suffix = int((kend - k2)[path == H.SPLIT].sum())
     split = path == H.SPLIT
+    lanes_dead = np.array([[bool(L.zdead_dead(float(c), float(g.g4[1]))) for c in w] for w in c2.reshape(-1, 64)])
+    mixed = lanes_dead.any(axis=1) & ~lanes_dead.all(axis=1)
     # LZQ_ZERO_SEG: a node of a whole-uniform (zero) pass runs without t and w, an FMA and an ADD fewer
     # on every node of those passes; set beside the PMC of profiles/round8/parent_pmc_summary.json
-    # (the six-operation node everywhere) this predicts the VALU per wave-node of the shipped kernel
-    with open(os.path.join(ROOT, "profiles", "round8", "parent_pmc_summary.json")) as f:
-        parent = json.load(f)
-    mix = dict(parent["valu_mix_per_wave_node"])
-    mix["fma_f64"] -= zero / nodes
-    mix["add_f64"] -= zero / nodes
+    # (the six-operation node everywhere) this predicts the VALU per wave-node of the kernel with it
+    p8 = _parent("round8")
+    mix8 = dict(p8["valu_mix_per_wave_node"])
+    mix8["fma_f64"] -= zero / nodes
+    mix8["add_f64"] -= zero / nodes
+    # LZQ_DEAD_SEG: a node of an all-dead pass runs F's fma alone: s (FMA), q (FMA) and v (MUL) are formed
+    # once per pass; against profiles/round9/parent_pmc_summary.json (the four-operation node on them)
+    p9 = _parent("round9")
+    mix9 = dict(p9["valu_mix_per_wave_node"])
+    mix9["fma_f64"] -= 2.0 * dead / nodes
+    mix9["mul_f64"] -= dead / nodes
     print(json.dumps({
         "passes": int(len(path)), "nodes_per_point": nodes,
-        "passes_whole_uniform": int((path == H.ZERO).sum()), "passes_clamp_free": int((path == H.FREE).sum()),
+        "passes_whole_uniform": int(((path == H.ZERO) | (path == H.DEAD)).sum()),
+        "passes_clamp_free": int((path == H.FREE).sum()),
         "passes_clamped": int(split.sum()), "clamped_passes_with_suffix": int((split & (k2 < kend)).sum()),
         "k2_of_clamped_passes": k2[split].tolist(),
         "uniform_nodes_whole_pass": zero, "uniform_nodes_clamped_suffix": suffix,
         "uniform_share": (zero + suffix) / nodes,
         "zero_pass_share": zero / nodes,
-        "predicted_valu_per_wave_node": parent["valu_insts_per_wave_node"] - 2.0 * zero / nodes,
-        "predicted_valu_mix_per_wave_node": mix}))
+        "predicted_valu_per_wave_node": p8["valu_insts_per_wave_node"] - 2.0 * zero / nodes,
+        "predicted_valu_mix_per_wave_node": mix8,
+        "passes_all_dead": int((path == H.DEAD).sum()), "all_dead_passes": np.flatnonzero(path == H.DEAD).tolist(),
+        "passes_live_zero": int((path == H.ZERO).sum()),
+        "passes_dead_and_live_lanes": int(mixed.sum()),
+        "all_dead_nodes": dead, "all_dead_share": dead / nodes,
+        "dead_seg_predicted_valu_per_wave_node": p9["valu_insts_per_wave_node"] - 3.0 * dead / nodes,
+        "dead_seg_predicted_valu_mix_per_wave_node": mix9}))
 
 
 if __name__ == "__main__":
