@@ -321,6 +321,36 @@ LZQ_HD double seg_node_zero(double c2N, double g, double Av, double Ts) {
 // a VGPR copy of it was kept live across the y-loop, at the cost of a spill.)
 LZQ_HD double seg_node_dead(double Av, double Ts) { return Ts * fma_vvs(Av, Av, kSqBeta); }
 
+// Frozen stretches.  gamma4 saturates, so g4_k moves ever less with k, and a lane's rounded
+// intermediate -- s = fma(c2N, g, A) on a zero pass, t = fma(c2N, g, M) on a clamp-free one -- stops
+// changing long before the pass ends (on small |c2N| it never changes).  Both are correctly rounded
+// and monotone in g for either sign of c2N, and g4 is non-decreasing up to the last executed node
+// g_last, so a lane whose value at g equals its value at g_last holds that value at every node in
+// between.  The tests evaluate the loop's own expression, so they are exact:
+//   frozen s (zero pass):  s, q = fma(s, s, beta) and v = T''[0] * q are per-lane constants from that
+//            node on -- seg_node_zero at g_last is their value, and a node is F's accumulate alone;
+//   frozen t (clamp-free pass):  t is, and with it the lookup (address, read, insert: seg_entry at
+//            that t) and w = (M + A) - t (seg_frozen_w); seg_node_frozen is the rest of the node, the
+//            general node's s, q and v on the same operands.
+LZQ_HD bool seg_frozen_s(double c2N, double g, double g_last, double Av) {
+  return __builtin_fma(c2N, g, Av) == __builtin_fma(c2N, g_last, Av);
+}
+LZQ_HD bool seg_frozen_t(double c2N, double g, double g_last, double Mv) {
+  return __builtin_fma(c2N, g, Mv) == __builtin_fma(c2N, g_last, Mv);
+}
+// a lane's held value on a frozen-s stretch: seg_node_zero at g_last, its instructions on its operands.
+// (beta is handed over as the fma's scalar operand, as in seg_node_dead and for its reason: formed
+// once per pass, a VGPR copy of beta was kept live across the y-loop and spilled.)
+LZQ_HD double seg_value_frozen_s(double c2N, double g_last, double Av, double Ts) {
+  const double s = __builtin_fma(c2N, g_last, Av);
+  return Ts * fma_vvs(s, s, kSqBeta);
+}
+LZQ_HD double seg_frozen_w(double t) { return (kTabMagic + kSqA) - t; }  // exact, as in the general node
+LZQ_HD double seg_node_frozen(double c2N, double g, double w, double Ts) {
+  const double s = __builtin_fma(c2N, g, w);
+  return Ts * __builtin_fma(s, s, kSqBeta);
+}
+
 // First node k2 in [0, kend], a multiple of `unroll` (which divides kend), with pred(g4(k2)); pred
 // must be monotone in k (false ... false true ... true); kend if it holds at no batch start.
 template <class Pred, class G4>

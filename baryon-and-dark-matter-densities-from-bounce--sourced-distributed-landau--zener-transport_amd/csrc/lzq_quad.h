@@ -80,6 +80,17 @@ constexpr int kWavesPerBlock = kBlock / kWaveSize;
 #ifndef LZQ_DEAD_SEG
 #define LZQ_DEAD_SEG 1
 #endif
+// the tail of a pass from the batch at which every lane's rounded intermediate has reached the value
+// it has at the last executed node (gamma4 saturates; seg_frozen_s / seg_frozen_t in lzq_exp2.h):
+//   1: zero passes -- s is frozen, so v is a per-lane constant and the node is F's accumulate alone
+//      (zsum_held; one FP64 operation per node instead of four);
+//   2: also clamp-free passes -- t is frozen, so the entry and w are per-lane constants and the node
+//      is s, q, v and F's fma (zsum_frozen_t; four FP64 operations instead of six, no lookup);
+//   0: off.  Needs LZQ_UNIFORM_SEG, LZQ_ZERO_SEG and LZQ_DEAD_SEG (without one of them it is off)
+#ifndef LZQ_FROZEN_SEG
+#define LZQ_FROZEN_SEG 2
+#endif
+constexpr int kFrozenSeg = (LZQ_UNIFORM_SEG != 0 && LZQ_ZERO_SEG != 0 && LZQ_DEAD_SEG != 0) ? LZQ_FROZEN_SEG : 0;
 constexpr int kKUnroll = LZQ_KUNROLL;  // z-nodes per scalar-load batch (must divide 1200)
 constexpr int kYB = LZQ_YB;            // y-nodes per lane per pass (independent chains)
 static_assert(kNZ % kKUnroll == 0, "z unroll must divide nz");
@@ -367,10 +378,15 @@ __device__ __forceinline__ double c2_scale() { return EXPV == kExpTable ? (doubl
 // s = fma(c2, g, A), q, v and F's fma, on the operands the six-operation node hands them
 // (LZQ_ZERO_SEG).  Where all 64 lanes of such a pass are dead (c2 = +0.0 in every lane, 24.8% of the
 // nodes) s = A as well, so q and v are one number for the pass and the node runs F's fma alone
-// (LZQ_DEAD_SEG, zsum_dead).  No node is skipped and the bits are the general loop's
+// (LZQ_DEAD_SEG, zsum_dead).  gamma4 saturates, so on the live zero passes every lane's s, and on the
+// clamp-free passes every lane's t, reaches the value it has at the last executed node well before
+// the pass ends: from that batch on, what depends on it is formed once per lane -- v on a zero pass,
+// whose node is then F's fma alone (18.0% of the nodes), the table entry and w on a clamp-free one,
+// whose node is then s, q, v and F's fma (6.4%) (LZQ_FROZEN_SEG, zsum_held, zsum_frozen_t).  No node
+// is skipped and the bits are the general loop's
 // (tests/test_zsum_segments_host.py, tests/test_zsum_zero_segment_host.py,
-// tests/test_zsum_dead_segment_host.py, tests/test_gpu_zsum_segments.py,
-// tests/test_gpu_zsum_zero_segment.py, tests/test_gpu_zsum_dead_segment.py).
+// tests/test_zsum_dead_segment_host.py, tests/test_zsum_frozen_host.py, tests/test_gpu_zsum_segments.py,
+// tests/test_gpu_zsum_zero_segment.py, tests/test_gpu_zsum_dead_segment.py, tests/test_gpu_zsum_frozen.py).
 template <int YB, int EXPV, bool CLAMP = true>
 __device__ __forceinline__ void zsum(const ZNode* __restrict__ zt, const double* tab, const double (&c2)[YB],
                                      double (&F)[YB], int kend, int kbeg = 0) {
@@ -505,6 +521,65 @@ __device__ __forceinline__ void zsum_dead(const ZNode* __restrict__ zt, double T
   }
 }
 
+// The held-value loop (LZQ_FROZEN_SEG >= 1): nodes kbeg .. kend of a zero pass on which every lane's
+// s = fma(c2, g, A) already has the value it has at the last executed node, so each lane's v is one
+// number on all of them (v[b]: seg_node_zero at that node, formed by the caller).  A node is F's
+// accumulate alone, F = fma(omega'_k, v, F), in node order, carrying on from kbeg: zsum_dead's loop
+// with a per-lane value, and these lanes are live, so F is kept.  No node is skipped.
+template <int YB>
+__device__ __forceinline__ void zsum_held(const ZNode* __restrict__ zt, const double (&v)[YB], double (&F)[YB], int kend,
+                                          int kbeg) {
+  if (kbeg == 0) {
+#pragma unroll
+    for (int b = 0; b < YB; ++b) F[b] = 0.0;
+  }
+  for (int k = kbeg; k < kend; k += kKUnroll) {
+    double om[kKUnroll];
+#pragma unroll
+    for (int kk = 0; kk < kKUnroll; ++kk) om[kk] = zt[k + kk].omega;
+#pragma unroll
+    for (int kk = 0; kk < kKUnroll; ++kk)
+#pragma unroll
+      for (int b = 0; b < YB; ++b) F[b] = __builtin_fma(om[kk], v[b], F[b]);
+  }
+}
+
+// The frozen-t loop (LZQ_FROZEN_SEG >= 2): nodes kbeg .. kend of a clamp-free pass on which every
+// lane's t = fma(c2, g, M) already has the value it has at the last executed node.  What the general
+// node derives from t alone is then fixed per lane -- the address, the ds_read and the exponent
+// insert (Ts[b]) and w = (M + A) - t (w[b]); the caller forms both with the general path's own
+// functions -- and a node is the general node's other four operations on the same operands in the
+// same order: s = fma(c2, g, w), q, v = Ts * q, and F's fma.  No node is skipped.
+template <int YB>
+__device__ __forceinline__ void zsum_frozen_t(const ZNode* __restrict__ zt, const double (&Ts)[YB], const double (&w)[YB],
+                                              const double (&c2)[YB], double (&F)[YB], int kend, int kbeg) {
+  if (kbeg == 0) {
+#pragma unroll
+    for (int b = 0; b < YB; ++b) F[b] = 0.0;
+  }
+  for (int k = kbeg; k < kend; k += kKUnroll) {
+    double g4[kKUnroll], om[kKUnroll];
+#pragma unroll
+    for (int kk = 0; kk < kKUnroll; ++kk) {
+      g4[kk] = zt[k + kk].g4;
+      om[kk] = zt[k + kk].omega;
+    }
+#pragma unroll
+    for (int kk = 0; kk < kKUnroll; ++kk)
+#pragma unroll
+      for (int b = 0; b < YB; ++b) F[b] = __builtin_fma(om[kk], seg_node_frozen(c2[b], g4[kk], w[b], Ts[b]), F[b]);
+  }
+}
+
+// The zero stretch's magic sum M as seg_entry's argument.  PINNED (the frozen paths are compiled in):
+// the dispatch's pinned VGPR copy of M, whose low word is the lookup's k = 0 -- as a literal, that 0
+// took a VGPR pair across the y-loop, and with the frozen paths' registers beside it, a spill.
+template <bool PINNED>
+__device__ __forceinline__ double zero_magic(double Mv) {
+  if constexpr (PINNED) return Mv;
+  else return kTabMagic;
+}
+
 // Pass-level wrapper: "dead" lanes, c2 * g4_1 <= -N*1077 (every node k >= 1 underflows to
 // exactly 0: g4 is increasing and omega_0 = 0), run the loop with c2 = 0 and are zeroed
 // afterwards -- the same instruction stream, the exact zero.
@@ -583,11 +658,63 @@ __device__ __forceinline__ void zsum_dispatch(const ZNode* __restrict__ zt, int 
 #pragma unroll
     for (int b = 0; b < YB; ++b) all_dead = all_dead && dead[b];
     if (LZQ_ZERO_SEG != 0 && LZQ_DEAD_SEG != 0 && __all(all_dead)) {
-      zsum_dead<YB>(zt, uniform(seg_entry(tab, kTabMagic)), F, kend);
+      zsum_dead<YB>(zt, uniform(seg_entry(tab, zero_magic<(kFrozenSeg > 0)>(Mv))), F, kend);
     } else if (__all(zero)) {
-      zsum_uniform<YB, LZQ_ZERO_SEG != 0>(zt, uniform(seg_entry(tab, kTabMagic)), c2e, F, kend, 0);
+      const double Ts0 = uniform(seg_entry(tab, zero_magic<(kFrozenSeg > 0)>(Mv)));
+      if constexpr (kFrozenSeg >= 1) {
+        // frozen s: from the first batch k3 at whose first node every lane's s equals its s at the
+        // last executed node, v is a per-lane constant (s is monotone in g, g4 non-decreasing); the
+        // nodes before k3 run the zero node, the rest F's accumulate alone.  k3 = 0: the whole pass
+        const double Av = vgpr_const(kSqA);
+        const double g_last = zt[kend > 0 ? kend - 1 : 0].g4;
+        const int k3 = seg_first_batch(
+            [&](double g) {
+              bool c = true;
+#pragma unroll
+              for (int b = 0; b < YB; ++b) c = c && seg_frozen_s(c2e[b], g, g_last, Av);
+              return __all(c) != 0;
+            },
+            [&](int k) { return zt[k].g4; }, kend, kKUnroll);
+        zsum_uniform<YB, true>(zt, Ts0, c2e, F, k3, 0);
+        if (k3 < kend) {
+          double v[YB];
+#pragma unroll
+          for (int b = 0; b < YB; ++b) v[b] = seg_value_frozen_s(c2e[b], g_last, Av, Ts0);
+          zsum_held<YB>(zt, v, F, kend, k3);
+        }
+      } else {
+        zsum_uniform<YB, LZQ_ZERO_SEG != 0>(zt, Ts0, c2e, F, kend, 0);
+      }
     } else if (__all(small)) {
-      zsum<YB, EXPV, false>(zt, tab, c2e, F, kend);
+      if constexpr (kFrozenSeg >= 2) {
+        // frozen t: from the first batch k3 at whose first node every lane's t equals its t at the
+        // last executed node, the lookup and w are per-lane constants; the nodes before k3 run the
+        // clamp-free general loop, the rest the four-operation node
+        const double g_last = zt[kend > 0 ? kend - 1 : 0].g4;
+        const int k3 = seg_first_batch(
+            [&](double g) {
+              bool c = true;
+#pragma unroll
+              for (int b = 0; b < YB; ++b) c = c && seg_frozen_t(c2e[b], g, g_last, Mv);
+              return __all(c) != 0;
+            },
+            [&](int k) { return zt[k].g4; }, kend, kKUnroll);
+        zsum<YB, EXPV, false>(zt, tab, c2e, F, k3);
+        if (k3 < kend) {
+          // (M pinned afresh: the copy above, kept live across the general loop, costs it a spill)
+          const double Mt = vgpr_const(kTabMagic);
+          double Tl[YB], wl[YB];
+#pragma unroll
+          for (int b = 0; b < YB; ++b) {
+            const double tl = __builtin_fma(c2e[b], g_last, Mt);
+            Tl[b] = seg_entry(tab, tl);  // per lane: the general path's address, load and insert
+            wl[b] = seg_frozen_w(tl);
+          }
+          zsum_frozen_t<YB>(zt, Tl, wl, c2e, F, kend, k3);
+        }
+      } else {
+        zsum<YB, EXPV, false>(zt, tab, c2e, F, kend);
+      }
     } else {
       const int k2 = seg_first_batch(
           [&](double g) {

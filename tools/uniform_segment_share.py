@@ -16,6 +16,14 @@ per node, two FMA and one MUL fewer), with the VALU count and mix their share pr
 of the build without that (profiles/round9/parent_pmc_summary.json), to set beside the shipped
 kernel's PMC (profiles/round6/pmc_summary.json).
 
+Last, the frozen tails (LZQ_FROZEN_SEG), planned by tests/zsum_frozen_host.cpp (the same predicates plus
+seg_frozen_s / seg_frozen_t): the live zero passes whose s = A at every node, the tails of the other
+live zero passes on which every lane's s has reached its last value (both run F's accumulate alone:
+two FMA and one MUL fewer per node), and the tails of the clamp-free passes on which every lane's t
+has (the four-operation node: one FMA, one ADD, two INT32 and the LDS read fewer), with the VALU count
+and the FMA / MUL / ADD / INT32 / LDS mix they predict from the PMC of the build without them
+(profiles/round10/parent_pmc_summary.json).
+
     python tools/uniform_segment_share.py
 """
 import json
@@ -27,6 +35,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import test_zsum_dead_segment_host as H  # noqa: E402
+import test_zsum_frozen_host as HF        # noqa: E402
 import zsum_ref as Z                      # noqa: E402
 
 
@@ -35,8 +44,37 @@ def _parent(rnd):
         return json.load(f)
 
 
+def frozen_counts(g, c2):
+    """The three stretches of LZQ_FROZEN_SEG on the passes of c2, and what they predict from the parent's PMC."""
+    _, _, plan = HF.run(HF.load_lib(), g, c2, HF.FROZEN, 0)
+    path, kend, k3 = plan[:, 0], plan[:, 2], plan[:, 3]
+    nodes = int(kend.sum())
+    whole = (path == HF.ZERO) & (k3 == 0)
+    ztail = (path == HF.ZERO) & (k3 > 0) & (k3 < kend)
+    ttail = (path == HF.FREE) & (k3 < kend)
+    n_whole, n_ztail, n_ttail = (int((kend - k3)[m].sum()) for m in (whole, ztail, ttail))
+    fs, ft = (n_whole + n_ztail) / nodes, n_ttail / nodes
+    p10 = _parent("round10")
+    mix = dict(p10["valu_mix_per_wave_node"])
+    mix["fma_f64"] -= 2.0 * fs + ft          # frozen s: s and q; frozen t: t
+    mix["mul_f64"] -= fs                     # frozen s: v
+    mix["add_f64"] -= ft                     # frozen t: w
+    mix["int32"] -= 2.0 * ft                 # frozen t: the address and the exponent insert
+    return {"frozen_seg": {
+        "passes_live_zero_whole_frozen": int(whole.sum()), "nodes_whole_frozen": n_whole,
+        "passes_live_zero_with_tail": int(ztail.sum()), "passes_live_zero_other": int(((path == HF.ZERO) & ~whole).sum()),
+        "nodes_zero_tails": n_ztail,
+        "passes_clamp_free": int((path == HF.FREE).sum()), "passes_clamp_free_with_tail": int(ttail.sum()),
+        "nodes_clamp_free_tails": n_ttail, "clamp_free_tail_lengths": sorted((kend - k3)[ttail].tolist()),
+        "frozen_s_share": fs, "frozen_t_share": ft,
+        "predicted_valu_per_wave_node": p10["valu_insts_per_wave_node"] - 3.0 * fs - 4.0 * ft,
+        "predicted_valu_per_wave_node_frozen_s_only": p10["valu_insts_per_wave_node"] - 3.0 * fs,
+        "predicted_valu_mix_per_wave_node": mix,
+        "predicted_lds_per_wave_node": p10["lds_insts_per_wave_node"] - ft}}
+
+
 def main():
-    B, Tp, I_p = 100.0, 100.0, 0.34                   # yields_config_equal_mass.json (C2's base)
+    B, Tp, I_p = 100.0, 100.0, 0.34                  # yields_config_equal_mass.json (C2's base)
     y_of = lambda T: 0.5 * B * ((Tp / T) ** 2 - 1.0)
     ys = np.linspace(max(y_of(5.0 * Tp), -80.0), min(y_of(1e-3 * Tp), 50.0), 8000)
     g = Z.grid(1200, 30.0)
@@ -65,7 +103,7 @@ def main():
     mix9 = dict(p9["valu_mix_per_wave_node"])
     mix9["fma_f64"] -= 2.0 * dead / nodes
     mix9["mul_f64"] -= dead / nodes
-    print(json.dumps({
+    print(json.dumps({**frozen_counts(g, c2),
         "passes": int(len(path)), "nodes_per_point": nodes,
         "passes_whole_uniform": int(((path == H.ZERO) | (path == H.DEAD)).sum()),
         "passes_clamp_free": int((path == H.FREE).sum()),
