@@ -351,6 +351,32 @@ LZQ_HD double seg_node_frozen(double c2N, double g, double w, double Ts) {
   return Ts * __builtin_fma(s, s, kSqBeta);
 }
 
+// Grouped passes (LZQ_GROUP_SEG; yb_group in lzq_quad.h).  A pass whose every node is F's accumulate
+// alone from node 0 -- all 64 lanes dead (zsum_dead), or a zero pass with k3 = 0 (zsum_held from the
+// first node) -- can share its sweep through z with its neighbours of the same kind.  seg_group_slot
+// classifies one lane of one untruncated pass with the single pass's own rules (g_0, g_1, g_last: g4 of
+// nodes 0, 1 and nz - 1, the last executed node, which is g_max):
+//   kGrpDead   the dispatch's dead rule, c2N g4_1 <= -N * 1077;
+//   kGrpWhole  with c2e = +0.0 on a dead lane as in the dispatch: the zero test at g_max and s frozen
+//              at the FIRST node, which is what makes the batch search return k3 = 0 (the predicate is
+//              monotone in k).  A dead lane passes both, so kGrpDead implies kGrpWhole.
+// seg_group_kind combines a lane's slots: the bits every one of its first g slots has.  A wave runs the
+// group as all-dead if every lane has kGrpDead, else as held if every lane has kGrpWhole, else not at all.
+constexpr int kGrpDead = 1, kGrpWhole = 2;
+constexpr double kDeadOctaves = 1077.0;  // zsum_dispatch's dead rule
+LZQ_HD int seg_group_slot(double c2N, double g_0, double g_1, double g_last, double Mv, double Av) {
+  const bool dead = c2N * g_1 <= -(double)kTabN * kDeadOctaves;
+  const double c2e = dead ? 0.0 : c2N;
+  const bool whole = seg_zero(c2e, g_last, Mv) && seg_frozen_s(c2e, g_0, g_last, Av);
+  return (dead ? kGrpDead : 0) | (whole ? kGrpWhole : 0);
+}
+// the classes of up to four slots packed two bits each (slot b in bits 2b, 2b + 1): AND over slots 0..g-1
+LZQ_HD int seg_group_kind(int packed, int g) {
+  int m = kGrpDead | kGrpWhole;
+  for (int b = 0; b < g; ++b) m &= packed >> (2 * b);
+  return m;
+}
+
 // First node k2 in [0, kend], a multiple of `unroll` (which divides kend), with pred(g4(k2)); pred
 // must be monotone in k (false ... false true ... true); kend if it holds at no batch start.
 template <class Pred, class G4>

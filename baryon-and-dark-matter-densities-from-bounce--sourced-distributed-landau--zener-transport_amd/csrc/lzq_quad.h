@@ -91,6 +91,18 @@ constexpr int kWavesPerBlock = kBlock / kWaveSize;
 #define LZQ_FROZEN_SEG 2
 #endif
 constexpr int kFrozenSeg = (LZQ_UNIFORM_SEG != 0 && LZQ_ZERO_SEG != 0 && LZQ_DEAD_SEG != 0) ? LZQ_FROZEN_SEG : 0;
+// runs of consecutive passes that are F's accumulate alone from node 0 (all 64 lanes dead, or every
+// lane's s frozen at A from the first node) are swept through z together, up to LZQ_GROUP_SEG (2 or 4)
+// passes at a time: each lane then carries that many independent F chains and every omega' feeds that
+// many fma (yb_group; the dense yb_wave only).  Each chain runs in node order from 0 and the passes are
+// integrated in pass order, so the bits are the single pass's and no node is skipped.  0: off.
+// Needs LZQ_FROZEN_SEG >= 1 and the default y-loop (LZQ_ACC_LDS, LZQ_Y_RECOMPUTE, no LZQ_YFACT_EARLY)
+#ifndef LZQ_GROUP_SEG
+#define LZQ_GROUP_SEG 4
+#endif
+static_assert(LZQ_GROUP_SEG == 0 || LZQ_GROUP_SEG == 2 || LZQ_GROUP_SEG == 4, "LZQ_GROUP_SEG is 0, 2 or 4");
+constexpr int kGroupSeg =
+    (kFrozenSeg >= 1 && LZQ_ACC_LDS != 0 && LZQ_Y_RECOMPUTE != 0 && LZQ_YFACT_EARLY == 0) ? LZQ_GROUP_SEG : 0;
 constexpr int kKUnroll = LZQ_KUNROLL;  // z-nodes per scalar-load batch (must divide 1200)
 constexpr int kYB = LZQ_YB;            // y-nodes per lane per pass (independent chains)
 static_assert(kNZ % kKUnroll == 0, "z unroll must divide nz");
@@ -387,6 +399,9 @@ __device__ __forceinline__ double c2_scale() { return EXPV == kExpTable ? (doubl
 // (tests/test_zsum_segments_host.py, tests/test_zsum_zero_segment_host.py,
 // tests/test_zsum_dead_segment_host.py, tests/test_zsum_frozen_host.py, tests/test_gpu_zsum_segments.py,
 // tests/test_gpu_zsum_zero_segment.py, tests/test_gpu_zsum_dead_segment.py, tests/test_gpu_zsum_frozen.py).
+// Those accumulate-only nodes (42.8%) are bound by the feed of omega', not by their one instruction: where
+// consecutive passes are accumulate-only from node 0, yb_wave sweeps up to four of them through z together
+// (LZQ_GROUP_SEG, yb_group below; tests/test_zsum_group_host.py, tests/test_gpu_zsum_group.py).
 template <int YB, int EXPV, bool CLAMP = true>
 __device__ __forceinline__ void zsum(const ZNode* __restrict__ zt, const double* tab, const double (&c2)[YB],
                                      double (&F)[YB], int kend, int kbeg = 0) {
@@ -509,6 +524,12 @@ template <int YB>
 __device__ __forceinline__ void zsum_dead(const ZNode* __restrict__ zt, double Ts, double (&F)[YB], int kend) {
 #pragma unroll
   for (int b = 0; b < YB; ++b) F[b] = 0.0;
+  // (YB > 1: the chains start from the same 0 and add the same terms; opaque starts keep them YB
+  // chains of YB fma per node -- dense work -- instead of one chain the compiler copies)
+  if constexpr (YB > 1) {
+#pragma unroll
+    for (int b = 0; b < YB; ++b) asm volatile("" : "+v"(F[b]));
+  }
   const double v0 = seg_node_dead(vgpr_const(kSqA), Ts);
   for (int k = 0; k < kend; k += kKUnroll) {
     double om[kKUnroll];
@@ -604,8 +625,11 @@ __device__ __forceinline__ double zero_magic(double Mv) {
 // tests/test_gpu_zsum.py: truncated tables against dense kernels, per value and through Y_B).
 // (Needs g4 non-decreasing over the grid: the host passes truncate = 0 for a grid whose
 // rounded g4 is not.)
+//
+// Returns whether the pass ran as F's accumulate alone from node 0 (all lanes dead, or a zero pass with
+// k3 = 0): what yb_wave's pass grouping (LZQ_GROUP_SEG) takes as its cue to try a group next.
 template <int YB, int EXPV, int NZ = 0>
-__device__ __forceinline__ void zsum_dispatch(const ZNode* __restrict__ zt, int nzp, const double* tab,
+__device__ __forceinline__ bool zsum_dispatch(const ZNode* __restrict__ zt, int nzp, const double* tab,
                                               const double (&c2)[YB], double (&F)[YB], int truncate = 0) {
   const int nz = NZ > 0 ? NZ : nzp;
   const double g_1 = zt[1].g4, g_max = zt[nz - 1].g4;
@@ -618,6 +642,7 @@ __device__ __forceinline__ void zsum_dispatch(const ZNode* __restrict__ zt, int 
     small = small && c2e[b] * g_max >= (double)kTabKMin;  // every node stays >= KMIN
   }
   int kend = nz;
+  bool acc_only = false;
   if (truncate) {
     // largest per-lane threshold g_thr = -1080 N / c2 (live lanes; dead lanes impose none,
     // c2 = 0 lanes never underflow)
@@ -659,6 +684,7 @@ __device__ __forceinline__ void zsum_dispatch(const ZNode* __restrict__ zt, int 
     for (int b = 0; b < YB; ++b) all_dead = all_dead && dead[b];
     if (LZQ_ZERO_SEG != 0 && LZQ_DEAD_SEG != 0 && __all(all_dead)) {
       zsum_dead<YB>(zt, uniform(seg_entry(tab, zero_magic<(kFrozenSeg > 0)>(Mv))), F, kend);
+      acc_only = true;
     } else if (__all(zero)) {
       const double Ts0 = uniform(seg_entry(tab, zero_magic<(kFrozenSeg > 0)>(Mv)));
       if constexpr (kFrozenSeg >= 1) {
@@ -675,6 +701,7 @@ __device__ __forceinline__ void zsum_dispatch(const ZNode* __restrict__ zt, int 
               return __all(c) != 0;
             },
             [&](int k) { return zt[k].g4; }, kend, kKUnroll);
+        acc_only = k3 == 0;
         zsum_uniform<YB, true>(zt, Ts0, c2e, F, k3, 0);
         if (k3 < kend) {
           double v[YB];
@@ -752,6 +779,7 @@ __device__ __forceinline__ void zsum_dispatch(const ZNode* __restrict__ zt, int 
   }
 #pragma unroll
   for (int b = 0; b < YB; ++b) F[b] = dead[b] ? 0.0 : F[b];
+  return acc_only;
 }
 
 // Stage the exp table (N doubles, see lzq_exp2.h) in LDS (every thread of the block must call this).
@@ -793,6 +821,99 @@ __device__ __forceinline__ int lane_id() {
   return l;
 }
 
+// Grouped passes (LZQ_GROUP_SEG): up to G consecutive full, untruncated passes of yb_wave from y-node
+// `base`, swept through z together where every one of them would run as F's accumulate alone from node 0.
+//
+// yb_group forms c2 of the passes exactly as the single pass does, classifies every lane and slot with
+// the single pass's own rules (seg_group_slot, lzq_exp2.h) and runs the largest of G, G/2, .. 2 leading
+// passes that fit the y-grid (`fit`: the full passes left from base, >= 2) and qualify.  The all-dead
+// group is zsum_dead<g>, the other zsum_held<g> from node 0 with each slot's held value; a dead lane
+// among live ones runs with c2e = +0.0 and is zeroed, as in zsum_dispatch: g chains per lane, each in
+// node order from 0.  The g passes are then integrated in ascending pass order with the single pass's
+// post-loop code (one unrolled copy per slot, shared by the group sizes: the code is what a launch
+// fetches from HBM besides its 48 B per point).  Returns the number of passes run and integrated;
+// 0: none qualifies, nothing was touched, and the caller runs the single pass.
+template <int G, int NZ, typename Win, typename Slot>
+__device__ __forceinline__ int yb_group(Slot* slots, int w, const ZNode* __restrict__ zt, int nzp, const double* tab,
+                                        int base, int fit) {
+  const int nz = NZ > 0 ? NZ : nzp;
+  double c2g[G];
+  int cls = 0;
+  {
+    const int lane = lane_id();
+    int wo = w;
+    asm volatile("" : "+s"(wo));
+    const QuadSetup& s = slots[wo].s;
+    const double g_0 = zt[0].g4, g_1 = zt[1].g4, g_last = zt[nz - 1].g4;
+    const double Mv = vgpr_const(kTabMagic), Av = vgpr_const(kSqA);
+#pragma unroll
+    for (int b = 0; b < G; ++b) {
+      // (a slot past `fit` is formed too -- y_node is arithmetic on j -- and never looked at)
+      const double yv = y_node(s, base + b * kWaveSize + lane);
+      const double ey = exp_sc(pymax(pymin(yv, 50.0), -50.0));               // fpy:161
+      c2g[b] = ((s.cneg * ey) * kLog2E) * c2_scale<kExpTable>();             // fpy:163, as in yb_wave
+      cls |= seg_group_slot(c2g[b], g_0, g_1, g_last, Mv, Av) << (2 * b);
+    }
+  }
+  int ran = 0;
+  bool all_dead = false;
+  if constexpr (G >= 4) {
+    if (fit >= 4) {
+      const int k4 = seg_group_kind(cls, 4);
+      all_dead = __all(k4 & kGrpDead) != 0;
+      if (all_dead || __all(k4 & kGrpWhole) != 0) ran = 4;
+    }
+  }
+  if (ran == 0) {
+    const int k2 = seg_group_kind(cls, 2);
+    all_dead = __all(k2 & kGrpDead) != 0;
+    if (all_dead || __all(k2 & kGrpWhole) != 0) ran = 2;
+  }
+  if (ran == 0) return 0;
+  double F[G];
+  {
+    const double Mv = vgpr_const(kTabMagic);
+    const double Ts0 = uniform(seg_entry(tab, Mv));
+    const double Av = vgpr_const(kSqA);
+    const double g_last = zt[nz - 1].g4;
+    double v[G] = {};
+    if (!all_dead) {
+#pragma unroll
+      for (int b = 0; b < G; ++b)
+        v[b] = seg_value_frozen_s(((cls >> (2 * b)) & kGrpDead) ? 0.0 : c2g[b], g_last, Av, Ts0);
+    }
+    if (G >= 4 && ran == 4) {
+      if (all_dead) zsum_dead<G>(zt, Ts0, F, nz);
+      else zsum_held<G>(zt, v, F, nz, 0);
+    } else {
+      double F2[2];
+      const double v2[2] = {v[0], v[1]};
+      if (all_dead) zsum_dead<2>(zt, Ts0, F2, nz);
+      else zsum_held<2>(zt, v2, F2, nz, 0);
+#pragma unroll
+      for (int b = 0; b < G; ++b) F[b] = b < 2 ? F2[b] : 0.0;
+    }
+  }
+  // (unrolled: rolled into one copy with F rotating down, the loop's hoisted constants spill)
+#pragma unroll
+  for (int b = 0; b < G; ++b) {
+    if (b < ran) {
+      const double Fb = ((cls >> (2 * b)) & kGrpDead) ? 0.0 : F[b];
+      int wr = w;
+      asm volatile("" : "+s"(wr));
+      const int lane2 = lane_id();
+      const QuadSetup& sr = slots[wr].s;
+      const int j = base + b * kWaveSize + lane2;  // < n: the group's passes are full
+      const double yv = y_node(sr, j);
+      const double ey = exp_sc(pymax(pymin(yv, 50.0), -50.0));
+      const double wt = y_weight(sr, j, yv);
+      const YFactors f = y_factors(slots[wr].s, yv, ey, wt, [&](double yy) { return Win::eval(slots[wr], yy); });
+      slots[wr].acc[lane2] = __builtin_fma(f.w, integrand_from(f, Fb), slots[wr].acc[lane2]);
+    }
+  }
+  return ran;
+}
+
 // Y_B of one point by one wavefront.  fpy:231-267
 //
 // Nothing but the z-loop's own state is held in registers across the z-loop (which needs ~60
@@ -825,7 +946,28 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
 #else
   double acc = 0.0;
 #endif
+  // grouped passes (LZQ_GROUP_SEG): the dense mode only -- the table and reuse modes are its controls.
+  // grp (wave-uniform): the pass before ran as the accumulate alone from node 0, or this is the first;
+  // only then is a group tried, so a point pays for a handful of classifications that fail
+  constexpr bool kGroupHere = kGroupSeg >= 2 && MODE == kYbDense && EXPV == kExpTable && YB == 1 && kSqForm;
+  // a window of the point's own (lzq_window.hip) groups two passes at most: with four, the F of the
+  // passes still to be integrated and the window's evaluation do not fit the 64 VGPRs (4 spilled)
+  constexpr int kGroupMax = __is_same(Win, SlotGaussWindow) ? kGroupSeg : (kGroupSeg < 2 ? kGroupSeg : 2);
+  [[maybe_unused]] bool grp = true;
   for (int base = 0; base < n; base += per_pass) {
+    if constexpr (kGroupHere) {
+      // under truncation kend differs from pass to pass and a dead pass is 8 nodes long: never grouped
+      if (grp && !truncate) {
+        int ran = 0;
+        const int fit = (n - base) / kWaveSize;  // the full passes left
+        if (fit >= 2) ran = yb_group<kGroupMax, NZ, Win>(slots, w, zt, nzp, tab, base, fit);
+        if (ran) {
+          base += (ran - 1) * per_pass;
+          continue;
+        }
+        grp = false;
+      }
+    }
     // only y, e^y and the weight stay live across the z-loop (LZQ_YFACT_EARLY=1: the 7
     // y-factors instead); the y-factors are formed after it
     double yv[YB], ey[YB], wt[YB];
@@ -858,7 +1000,7 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
         fy[b] = y_factors(s, yv[b], ey[b], wt[b]);
 #endif
       }
-      zsum_dispatch<YB, EXPV, NZ>(zt, nzp, tab, c2, F, truncate);
+      grp = zsum_dispatch<YB, EXPV, NZ>(zt, nzp, tab, c2, F, truncate);
       if constexpr (MODE == kYbTable) {
 #pragma unroll
         for (int b = 0; b < YB; ++b) {

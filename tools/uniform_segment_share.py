@@ -24,6 +24,11 @@ has (the four-operation node: one FMA, one ADD, two INT32 and the LDS read fewer
 and the FMA / MUL / ADD / INT32 / LDS mix they predict from the PMC of the build without them
 (profiles/round10/parent_pmc_summary.json).
 
+And the grouped passes (LZQ_GROUP_SEG), planned by tests/zsum_group_host.cpp (yb_wave's pass loop with
+seg_group_slot / seg_group_kind): how many of the point's passes run in groups of four and two, frozen
+and dead, their share of the (pass, node) pairs, and the classifications that come to nothing.  The
+instruction counts do not change; what the groups buy is issue time (profiles/round11).
+
     python tools/uniform_segment_share.py
 """
 import json
@@ -36,6 +41,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import test_zsum_dead_segment_host as H  # noqa: E402
 import test_zsum_frozen_host as HF        # noqa: E402
+import test_zsum_group_host as HG         # noqa: E402
 import zsum_ref as Z                      # noqa: E402
 
 
@@ -73,12 +79,28 @@ def frozen_counts(g, c2):
         "predicted_lds_per_wave_node": p10["lds_insts_per_wave_node"] - ft}}
 
 
+def group_counts(g, c2_nodes, gmax=4):
+    """The grouped passes of LZQ_GROUP_SEG = gmax on the point's y-nodes c2_nodes (unpadded)."""
+    _, _, _, plan = HG.run(HG.load_lib(), g, c2_nodes, gmax)
+    size, path, tried = plan[:, 0], plan[:, 1], plan[:, 2]
+    groups = HG.group_counts(plan)
+    n_grouped = int((size > 1).sum())
+    return {"group_seg": {
+        "max_group": gmax, "passes": int(len(plan)), "passes_grouped": n_grouped,
+        "passes_grouped_frozen": int(((size > 1) & (path == HG.ZERO)).sum()),
+        "passes_grouped_dead": int(((size > 1) & (path == HG.DEAD)).sum()),
+        "groups": {f"{s}x_{'dead' if p == HG.DEAD else 'frozen'}": n for (s, p), n in sorted(groups.items())},
+        "grouped_node_share": n_grouped / len(plan),
+        "classifications_refused": int(((size == 1) & (tried == 1)).sum())}}
+
+
 def main():
     B, Tp, I_p = 100.0, 100.0, 0.34                  # yields_config_equal_mass.json (C2's base)
     y_of = lambda T: 0.5 * B * ((Tp / T) ** 2 - 1.0)
     ys = np.linspace(max(y_of(5.0 * Tp), -80.0), min(y_of(1e-3 * Tp), 50.0), 8000)
     g = Z.grid(1200, 30.0)
     c2 = ((-(I_p / 6.0) * np.exp(np.clip(ys, -50.0, 50.0))) * Z.LOG2E) * 8192.0
+    grouped = group_counts(g, c2)
     c2 = np.concatenate([c2, np.full(-len(c2) % 64, c2[-1])])      # tail lanes recompute the last node
     L = H.load_lib()
     _, _, plan = H.run(L, g, c2, H.DEADSEG, 0)
@@ -103,7 +125,7 @@ def main():
     mix9 = dict(p9["valu_mix_per_wave_node"])
     mix9["fma_f64"] -= 2.0 * dead / nodes
     mix9["mul_f64"] -= dead / nodes
-    print(json.dumps({**frozen_counts(g, c2),
+    print(json.dumps({**grouped, **frozen_counts(g, c2),
         "passes": int(len(path)), "nodes_per_point": nodes,
         "passes_whole_uniform": int(((path == H.ZERO) | (path == H.DEAD)).sum()),
         "passes_clamp_free": int((path == H.FREE).sum()),
