@@ -149,7 +149,7 @@ LZQ_NZ_MAX = 1 << 22
 ODE_NT_MAX = 1 << 20
 REUSE_TABLE_HEADER = 6  # LZQ_REUSE_TABLE_HEADER
 (TUNE_EXP, TUNE_TRUNCATE, TUNE_ODE_COOP, TUNE_ODE_LAUNCH_STEPS, TUNE_PROFILE_FLAT, TUNE_ODE_TP_INTERVAL,
- TUNE_ODE_TABLE_WIDE) = 0, 1, 2, 3, 4, 5, 6  # enum lzq_tune_key
+ TUNE_ODE_TABLE_WIDE, TUNE_CONT_SKIP) = 0, 1, 2, 3, 4, 5, 6, 7  # enum lzq_tune_key
 ODE_MAX_LAUNCHES = 65536  # lzq_ode_*: max_steps <= 65536 x 2^(launch log2)
 # tuning state that changes result bits (the inner-loop exponential, ~1e-14): part of the
 # sweep checkpoint key (sweep.spec_key); Engine.tune_exp keeps it current
@@ -193,6 +193,9 @@ EXPORTS = ("lzq_abi_version", "lzq_last_error", "lzq_init", "lzq_zgrid_init", "l
            "lzq_sweep_grid_window", "lzq_sweep_grid_reuse_window", "lzq_sweep_grid_ztables_window",
            "lzq_sweep_grid_from_ztables_window", "lzq_window_grid_blocks_host", "lzq_window_grid_check_host",
            "lzq_sweep_grid_solve", "lzq_solve_check_host",
+           "lzq_cont_tables", "lzq_aov_cont_host", "lzq_aov_batch_cont", "lzq_sweep_grid_ztables_cont",
+           "lzq_sweep_grid_from_ztables_cont", "lzq_sweep_grid_cont", "lzq_yields_batch_cont",
+           "lzq_sweep_grid_solve_cont",
            "lzq_lz_propagate", "lzq_lz_propagate_v", "lzq_ode_tables", "lzq_ode_integrate", "lzq_ode_integrate_shared", "lzq_ode_rows", "lzq_ode_integrate_rows", "lzq_ode_integrate_tp", "lzq_ode_quadrature", "lzq_ode_batch",
            "lzq_ode_aov_T", "lzq_ode_rhs", "lzq_profile_splines", "lzq_profile_crossings",
            "lzq_lz_propagate_profile",
@@ -274,6 +277,17 @@ def load(path: str | None = None):
     L.lzq_sweep_grid_solve.argtypes = [P(LzqPoint), P(LzqWindow), P(LzqAxis), i32, P(LzqSolve), i64, i64, i32, i32, d,
                                        vp, vp, i64, P(LzqWindowTables), vp, vp, vp]
     L.lzq_solve_check_host.argtypes = [P(LzqSolve), P(LzqWindow), P(LzqAxis), i32]
+    L.lzq_cont_tables.argtypes = [d, P(d), P(d), P(d), P(i32)]
+    L.lzq_aov_cont_host.argtypes = [P(LzqPoint), P(LzqAovParams), vp, i64, d, vp]
+    L.lzq_aov_batch_cont.argtypes = [P(LzqPoint), P(LzqAovParams), vp, i64, d, vp, vp]
+    L.lzq_sweep_grid_ztables_cont.argtypes = [P(LzqPoint), P(LzqAxis), i32, i32, d, vp, i64, vp]
+    L.lzq_sweep_grid_from_ztables_cont.argtypes = [P(LzqPoint), P(LzqWindow), P(LzqAxis), i32, i64, i64, i32, d, vp,
+                                                   vp, i64, P(LzqWindowTables), vp, vp]
+    L.lzq_sweep_grid_cont.argtypes = [P(LzqPoint), P(LzqWindow), P(LzqAxis), i32, i64, i64, i32, d, vp, vp, i64,
+                                      P(LzqWindowTables), vp, vp]
+    L.lzq_yields_batch_cont.argtypes = [vp, i64, i32, d, vp, vp, vp, i64, vp, i64, vp, P(LzqWindowTables), vp, vp]
+    L.lzq_sweep_grid_solve_cont.argtypes = [P(LzqPoint), P(LzqWindow), P(LzqAxis), i32, P(LzqSolve), i64, i64, i32, d,
+                                            vp, vp, i64, P(LzqWindowTables), vp, vp, vp]
     L.lzq_lz_propagate.argtypes = [vp, vp, vp, i64, i32, d, d, i32, vp, vp]
     L.lzq_lz_propagate_v.argtypes = [vp, vp, vp, vp, i64, i32, d, i32, vp, vp]
     L.lzq_ode_tables.argtypes = [vp, i64, vp, vp, i32, i32, d, vp, vp, i64, vp, vp]
@@ -346,3 +360,34 @@ def zgrid(nz, z_max) -> tuple[int, float]:
     if n < 0:
         raise ValueError(f"Number of samples, {n}, must be non-negative.")
     return int(n), float(z_max)
+
+
+def cont_z_max(z_max) -> float:
+    """Validate the z_max of the continuum z rule (include/lzq.h): a finite float > 0 (ValueError)."""
+    import math
+    z = float(z_max)
+    if not (math.isfinite(z) and z > 0.0):
+        raise ValueError(f"continuum z rule: z_max = {z!r} must be finite and > 0")
+    return z
+
+
+def cont_tables(z_max: float = LZQ_Z_MAX) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Host copies of the continuum z rule's tables for z_max (lzq_cont_tables; csrc/lzq_cont.h):
+    the nodes z (ascending in (0, z_max)), gamma4 = gamma(4, z) and omega = z^2 e^-z w.  No GPU."""
+    n = ctypes.c_int32(0)
+    dp = ctypes.POINTER(ctypes.c_double)
+    check(load().lzq_cont_tables(float(z_max), None, None, None, ctypes.byref(n)))
+    z, g4, om = (np.empty(n.value) for _ in range(3))
+    check(load().lzq_cont_tables(float(z_max), z.ctypes.data_as(dp), g4.ctypes.data_as(dp), om.ctypes.data_as(dp),
+                                 ctypes.byref(n)))
+    return z, g4, om
+
+
+def aov_cont_host(kernel, ys, z_max: float = LZQ_Z_MAX) -> np.ndarray:
+    """A/V_cont(y) of include/lzq.h from its host build (lzq_aov_cont_host: libm exp, no GPU).
+    kernel: a mapping with AOV_FIELDS."""
+    a = LzqAovParams(*(float(kernel[f]) for f in AOV_FIELDS))
+    y = np.ascontiguousarray(ys, dtype=np.float64).reshape(-1)
+    out = np.empty_like(y)
+    check(load().lzq_aov_cont_host(None, ctypes.byref(a), y.ctypes.data, y.size, float(z_max), out.ctypes.data))
+    return out

@@ -25,7 +25,12 @@ class AoverVKernel:
     by the library (lzq_ztables) and uploaded once per grid; every A_over_V_y runs on the GPU."""
 
     def __init__(self, I_p: float, beta_over_H: float, T_p: float, v_w: float, g_star: float,
-                 z_max: float = LZQ_ZMAX, nz: int = LZQ_NZ):
+                 z_max: float = LZQ_ZMAX, nz: int = LZQ_NZ, continuum: bool = False):
+        # continuum: the z-sum on the continuum z rule of z_max (include/lzq.h "A/V in the continuum
+        # limit"): z and g4 are then that rule's nodes and its stable gamma(4, z), and nz is not read
+        self.continuum = bool(continuum)
+        if self.continuum:
+            z_max = _native.cont_z_max(z_max)
         self.nz, self.z_max = _native.zgrid(nz, z_max)  # numpy linspace's TypeError / ValueError
         self.I_p = I_p
         self.beta_over_H = beta_over_H
@@ -48,7 +53,7 @@ class AoverVKernel:
 
     def _ztables(self):
         if self._tables is None:
-            self._tables = _native.ztables(self.nz, self.z_max)
+            self._tables = _native.cont_tables(self.z_max) if self.continuum else _native.ztables(self.nz, self.z_max)
         return self._tables
 
     def A_over_V_y(self, y: float) -> float:
@@ -57,7 +62,7 @@ class AoverVKernel:
     def A_over_V_ys(self, ys) -> np.ndarray:
         """Batched fpy:158-165 (one GPU lane per y), with this kernel's own I_p, beta_over_H, T_p,
         v_w and g_star (lzq_aov_batch's lzq_aov_params block)."""
-        return default_engine().aov(self, ys, nz=self.nz, z_max=self.z_max).cpu().numpy()
+        return default_engine().aov(self, ys, nz=self.nz, z_max=self.z_max, continuum=self.continuum).cpu().numpy()
 
 
 class BoltzmannSystem:
@@ -83,6 +88,12 @@ class BoltzmannSystem:
         if self.window is not None:
             raise NotImplementedError(f"{who}: the ODE operators keep the reference's Gaussian window (fpy:226-228); "
                                       "set bs.window = None")
+
+    def _no_continuum(self, who: str) -> None:
+        if getattr(self.aov, "continuum", False):
+            raise NotImplementedError(f"{who}: a continuum bs.aov is evaluated by its own A_over_V_y only; the yields on "
+                                      "the continuum z rule are Engine.yields(continuum=True) (main()'s window, shared "
+                                      "z-sum tables), and the ODE tables stay on the linspace grids")
 
     def _own_aov(self) -> bool:
         a, c = self.aov, self.cfg
@@ -118,6 +129,7 @@ class BoltzmannSystem:
 
     def integrate_YB_by_quadrature(self, T_lo: float, T_hi: float, n_y: int = 6000) -> float:
         """fpy:231-267 on the GPU (one wavefront)."""
+        self._no_continuum("integrate_YB_by_quadrature")
         rec = to_point(self.cfg, P=self.P)
         if self.window is not None:
             if not self._own_aov():
@@ -138,6 +150,7 @@ class BoltzmannSystem:
         least 4 knots for the cubic form the library evaluates)."""
         import operator
         self._no_window("build_tables")
+        self._no_continuum("build_tables")
         n = operator.index(n)
         if not 4 <= n <= _native.ODE_NT_MAX:
             raise ValueError(f"build_tables: n = {n} outside [4, {_native.ODE_NT_MAX}]")

@@ -32,6 +32,9 @@ def main(argv=None):
                     help="Try to compute P_chi_to_B from local LZ modules using this profile CSV.")
     ap.add_argument("--diagnostics", action="store_true",
                     help="Print a small table of y(T), A/V(T), J_chi(T), S_B(T) around T_p.")
+    ap.add_argument("--continuum", action="store_true",
+                    help="A/V's z-sum as a converged z-integral (the continuum z rule, include/lzq.h) in place of "
+                         "the reference's 1200-node grid; the output keeps its format.  Quadrature path only.")
     args = ap.parse_args(argv)
 
     if args.write_template:
@@ -50,7 +53,11 @@ def main(argv=None):
             raise UnboundLocalError("local variable 'Ychi_fin' referenced before assignment")
     eng = default_engine()
     if fast_path_ok(cfg):
-        table = eng.yields(to_point(cfg, P=P_used), n_y=8000)  # fpy:374 + fpy:376-417 on the GPU
+        # fpy:374 + fpy:376-417 on the GPU
+        table = eng.yields(to_point(cfg, P=P_used), n_y=8000, continuum=args.continuum)
+    elif args.continuum:
+        raise NotImplementedError("--continuum: this configuration takes the ODE fallback (sigma_v / Gamma_wash / "
+                                  "depletion), whose spline tables are built on the reference's z grid only")
     else:
         # fpy:385-410: build_tables + Radau, then fpy:412-417; one point: Engine.ode integrates it
         # parallel in time (lzq_ode_integrate_tp, the sequential steps' bits)
@@ -79,7 +86,7 @@ def main(argv=None):
         print("\n# Diagnostics around percolation")
         Ts = np.geomspace(cfg.T_p_GeV * 0.5, cfg.T_p_GeV * 2.0, 21)
         ys = [y_of_T(T, cfg.T_p_GeV, cfg.beta_over_H) for T in Ts]
-        aovs = eng.aov(cfg, ys).cpu().numpy()
+        aovs = eng.aov(cfg, ys, continuum=args.continuum).cpu().numpy()
         Js = eng.jchi(cfg, Ts).cpu().numpy()
         print(" T/Tp      y(T)        A/V [GeV]         J_chi [GeV^3]      S_B [GeV^3]")
         for T, y, aov, J in zip(Ts, ys, aovs, Js):

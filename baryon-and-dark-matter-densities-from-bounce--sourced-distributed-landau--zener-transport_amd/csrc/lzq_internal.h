@@ -69,6 +69,33 @@ int launch_grid_solve(const lzq_point& base, const lzq_window* base_win, const G
                       const double* d_P, double key_nz, double key_z_max, const double* d_work, int64_t stride,
                       lzq_yield* d_out, lzq_solve_result* d_sol, hipStream_t s);
 
+// lzq_cont.hip: the continuum z rule (lzq_cont.h).  Its node table goes through the z-sum table,
+// integration, window and solve kernels of the linspace grids, so the *_cont entry points are the
+// host wrappers below (lzq_kernels.hip) with cont = true: the z grid is then cont_grid_for's and nz
+// is not read.  cont = false is the public entry point of the same name, unchanged.
+constexpr double kContKeyNz = -1.0;  // a continuum table's header nz slot: no linspace grid has it
+extern int g_cont_skip;              // lzq_tune(LZQ_TUNE_CONT_SKIP)
+// the device image of z_max's table on device dev (built and uploaded once per (device, z_max))
+int cont_grid_for(int dev, double z_max, const ZNode** zt, int32_t* nzp);
+// the current device's exp table and the tuned variant, its tables initialised (lzq_kernels.hip)
+int device_exp_table(int* dev, const double** gtab, int* exp_variant);
+// The live-range z-sum table kernel: table t of the grid (pts NULL) or of point pts[reps[t]].
+int launch_cont_ztables(int exp_variant, const lzq_point* base, const GridSpec* grid, const lzq_point* pts,
+                        const int64_t* reps, int64_t n_tab, int32_t n_y, int64_t tstride, const ZNode* zt, int32_t nzp,
+                        double key_z_max, const double* gtab, double* d_work, hipStream_t s);
+int yields_batch_reuse(const lzq_point* d_points, int64_t n, int32_t n_y, int32_t nz, double z_max, const double* d_P,
+                       const int64_t* d_rep, const int32_t* d_table_index, int64_t n_tables, double* d_work,
+                       int64_t work_doubles, const lzq_window* d_win, const lzq_window_tables* wt, lzq_yield* d_out,
+                       void* stream, bool cont, const char* fn);
+int sweep_grid_reuse_parts(const lzq_point* base, const lzq_axis* axes, int32_t n_axes, int64_t start, int64_t count,
+                           int32_t n_y, int32_t nz, double z_max, const double* d_P, double* d_work,
+                           int64_t work_doubles, lzq_yield* d_out, void* stream, int parts, const char* fn,
+                           bool window_axes, const lzq_window* base_win, const lzq_window_tables* d_tables, bool cont);
+int sweep_grid_solve(const lzq_point* base, const lzq_window* base_win, const lzq_axis* axes, int32_t n_axes,
+                     const lzq_solve* solve, int64_t start, int64_t count, int32_t n_y, int32_t nz, double z_max,
+                     const double* d_P, const double* d_work, int64_t work_doubles, const lzq_window_tables* d_tables,
+                     lzq_yield* d_out, lzq_solve_result* d_sol, void* stream, bool cont, const char* fn);
+
 // Longest-first launch order (lzq_propagator.hip): cost bins per point (0 = costliest, kCostBins
 // of them) and their histogram -> offs (kCostBins scratch) and order[n] (a counting sort: one
 // scan, one scatter; stable across bins, atomics order within one).  Sets lzq_last_error.

@@ -119,27 +119,7 @@ __global__ __launch_bounds__(kBlock, LZQ_MIN_WAVES) void yields_grid_kernel(lzq_
 // is bit-identical to lzq_sweep_grid.  Table t: kTabHdr header doubles (the y-grid and c of the
 // QuadSetup it was made for, and the z grid's (nz, z_max); a point whose own setup or grid
 // differs gets NaN yields, never a wrong table), then its F values.
-constexpr int kTabHdr = 6;
-static_assert(kTabHdr == LZQ_REUSE_TABLE_HEADER, "include/lzq.h");
-
-// The z grid a table is made for, as its header stores it.
-struct ZKey {
-  double nz, z_max;
-};
-
-__device__ __forceinline__ int64_t table_of(const GridSpec& g, int64_t idx) {
-  int64_t t = 0;
-  for (int a = 0; a < g.n_axes; ++a) t += ((idx / g.stride[a]) % g.n[a]) * g.tstride[a];
-  return t;
-}
-
-// flat grid index of table t's representative (every other axis at its first value)
-__device__ __forceinline__ int64_t table_rep(const GridSpec& g, int64_t t) {
-  int64_t idx = 0;
-  for (int a = 0; a < g.n_axes; ++a)
-    if (g.tstride[a]) idx += ((t / g.tstride[a]) % g.n[a]) * g.stride[a];
-  return idx;
-}
+// (kTabHdr, ZKey, table_of and table_rep: lzq_quad.h, shared with lzq_cont.hip)
 
 // Table t of one wavefront: header + the F values of the point parked in the wave's slot.
 template <int EXPV>
@@ -506,10 +486,16 @@ bool is_default_grid(int32_t nz, double z_max) { return nz == LZQ_NZ && z_max ==
 // The device tables of (nz, z_max) on the current device: the default grid's (lzq_init), or a
 // runtime grid's, built and uploaded once per (device, nz, z_max) (a synchronous copy: call
 // lzq_zgrid_init before capturing launches into a graph).
-int zgrid_for(int32_t nz, double z_max, DevZGrid& g, int* dev_out) {
+// cont (the *_cont entry points only; nz is not read): the continuum node table of z_max
+// (lzq_cont.hip), keyed in a table's header by an nz no linspace grid has.
+int zgrid_for(int32_t nz, double z_max, DevZGrid& g, int* dev_out, bool cont = false) {
   int dev, rc = ensure_device(&dev);
   if (rc) return rc;
   if (dev_out) *dev_out = dev;
+  if (cont) {
+    g.key = lzq::ZKey{lzq::kContKeyNz, z_max};
+    return lzq::cont_grid_for(dev, z_max, &g.zt, &g.nzp);  // is_default = false, monotone = true
+  }
   g.key = lzq::ZKey{(double)nz, z_max};
   if (is_default_grid(nz, z_max)) {
     g.zt = g_dev_tab[dev];
@@ -550,6 +536,14 @@ constexpr int64_t kMaxGrid = 2147483647LL;
 }  // namespace
 
 int lzq_set_error(int code, const char* msg) { return fail(code, "%s", msg); }
+
+int lzq::device_exp_table(int* dev, const double** gtab, int* exp_variant) {
+  const int rc = ensure_device(dev);
+  if (rc) return rc;
+  *gtab = exp_table(*dev);
+  *exp_variant = g_exp_variant;
+  return LZQ_OK;
+}
 
 int lzq::launch_ode_aov_tables(const lzq_point* d_points, int64_t n, const double* d_T_lo, const double* d_T_hi,
                                int32_t nt, int32_t nz, double z_max, const lzq_aov_params* d_aov, double* d_work,
@@ -644,6 +638,12 @@ int lzq_tune(int32_t key, int32_t value) {
     if (value != 0 && value != 1) return fail(LZQ_EINVAL, "lzq_tune: ode_coop must be 0 or 1, got %d", value);
     int prev = lzq::g_ode_coop;
     lzq::g_ode_coop = value;
+    return prev;
+  }
+  if (key == LZQ_TUNE_CONT_SKIP) {
+    if (value != 0 && value != 1) return fail(LZQ_EINVAL, "lzq_tune: cont_skip must be 0 or 1, got %d", value);
+    int prev = lzq::g_cont_skip;
+    lzq::g_cont_skip = value;
     return prev;
   }
   return fail(LZQ_EINVAL, "lzq_tune: unknown key %d", key);
@@ -844,26 +844,34 @@ int lzq_sweep_grid(const lzq_point* base, const lzq_axis* axes, int32_t n_axes, 
 
 // lzq_yields_batch_reuse, and with d_win lzq_yields_batch_reuse_window (the tables are the same;
 // the integration takes each point's window from its block, lzq_window.hip)
-static int yields_batch_reuse(const lzq_point* d_points, int64_t n, int32_t n_y, int32_t nz, double z_max,
-                              const double* d_P, const int64_t* d_rep, const int32_t* d_table_index, int64_t n_tables,
-                              double* d_work, int64_t work_doubles, const lzq_window* d_win,
-                              const lzq_window_tables* wt, lzq_yield* d_out, void* stream) {
+// (cont: lzq_yields_batch_cont, the tables on the continuum node rule -- lzq_internal.h)
+}  // extern "C"
+int lzq::yields_batch_reuse(const lzq_point* d_points, int64_t n, int32_t n_y, int32_t nz, double z_max,
+                            const double* d_P, const int64_t* d_rep, const int32_t* d_table_index, int64_t n_tables,
+                            double* d_work, int64_t work_doubles, const lzq_window* d_win,
+                            const lzq_window_tables* wt, lzq_yield* d_out, void* stream, bool cont, const char* fn) {
   if (n < 0 || n_tables < 0 || (n > 0 && (!d_points || !d_out || !d_rep || !d_table_index || n_tables == 0)))
-    return fail(LZQ_EINVAL, "lzq_yields_batch_reuse: bad arguments");
+    return fail(LZQ_EINVAL, "%s: bad arguments", fn);
   const int64_t stride = (n_y > LZQ_NY_MIN ? n_y : LZQ_NY_MIN) + lzq::kTabHdr;
-  if (n_tables > INT64_MAX / stride) return fail(LZQ_EINVAL, "lzq_yields_batch_reuse: too many tables");
+  if (n_tables > INT64_MAX / stride) return fail(LZQ_EINVAL, "%s: too many tables", fn);
   if (n > 0 && (!d_work || work_doubles < n_tables * stride))
-    return fail(LZQ_EINVAL, "lzq_yields_batch_reuse: workspace of %lld doubles < %lld needed", (long long)work_doubles,
+    return fail(LZQ_EINVAL, "%s: workspace of %lld doubles < %lld needed", fn, (long long)work_doubles,
                 (long long)(n_tables * stride));
   if (n == 0) return LZQ_OK;
   int dev;
   DevZGrid g;
-  int rc = zgrid_for(nz, z_max, g, &dev);
+  int rc = zgrid_for(nz, z_max, g, &dev, cont);
   if (rc) return rc;
   const int64_t nbt = blocks_for(n_tables, lzq::kWavesPerBlock), nb = blocks_for(n, lzq::kWavesPerBlock);
-  if (nbt > kMaxGrid || nb > kMaxGrid) return fail(LZQ_EINVAL, "lzq_yields_batch_reuse: too large for one launch");
-  const int trunc = g.monotone ? 1 : 0;  // bit-identical to the dense sums either way
-  if (g_exp_variant == lzq::kExpTable)
+  if (nbt > kMaxGrid || nb > kMaxGrid) return fail(LZQ_EINVAL, "%s: too large for one launch", fn);
+  // bit-identical to the dense sums either way; a continuum table with LZQ_TUNE_CONT_SKIP = 0 is the
+  // every-node control
+  const int trunc = cont ? 0 : (g.monotone ? 1 : 0);
+  if (cont && lzq::g_cont_skip) {
+    rc = lzq::launch_cont_ztables(g_exp_variant, nullptr, nullptr, d_points, d_rep, n_tables, n_y, stride, g.zt, g.nzp,
+                                  g.key.z_max, exp_table(dev), d_work, (hipStream_t)stream);
+    if (rc) return rc;
+  } else if (g_exp_variant == lzq::kExpTable)
     hipLaunchKernelGGL((lzq::points_ztable_kernel<lzq::kExpTable>), dim3((unsigned)nbt), dim3(lzq::kBlock), 0,
                        (hipStream_t)stream, d_points, d_rep, n_tables, n_y, stride, g.zt, g.nzp, g.key,
                        exp_table(dev), d_work, trunc);
@@ -880,12 +888,13 @@ static int yields_batch_reuse(const lzq_point* d_points, int64_t n, int32_t n_y,
   LZQ_HIP(hipGetLastError());
   return LZQ_OK;
 }
+extern "C" {
 
 int lzq_yields_batch_reuse(const lzq_point* d_points, int64_t n, int32_t n_y, int32_t nz, double z_max,
                            const double* d_P, const int64_t* d_rep, const int32_t* d_table_index, int64_t n_tables,
                            double* d_work, int64_t work_doubles, lzq_yield* d_out, void* stream) {
-  return yields_batch_reuse(d_points, n, n_y, nz, z_max, d_P, d_rep, d_table_index, n_tables, d_work, work_doubles,
-                            nullptr, nullptr, d_out, stream);
+  return lzq::yields_batch_reuse(d_points, n, n_y, nz, z_max, d_P, d_rep, d_table_index, n_tables, d_work,
+                                 work_doubles, nullptr, nullptr, d_out, stream, false, "lzq_yields_batch_reuse");
 }
 
 int lzq_yields_batch_reuse_window(const lzq_point* d_points, int64_t n, int32_t n_y, int32_t nz, double z_max,
@@ -896,8 +905,8 @@ int lzq_yields_batch_reuse_window(const lzq_point* d_points, int64_t n, int32_t 
   lzq_window_tables wt;
   const int rc = lzq::window_tables_arg(d_tables, "lzq_yields_batch_reuse_window", wt);
   if (rc) return rc;
-  return yields_batch_reuse(d_points, n, n_y, nz, z_max, d_P, d_rep, d_table_index, n_tables, d_work, work_doubles,
-                            d_win, &wt, d_out, stream);
+  return lzq::yields_batch_reuse(d_points, n, n_y, nz, z_max, d_P, d_rep, d_table_index, n_tables, d_work,
+                                 work_doubles, d_win, &wt, d_out, stream, false, "lzq_yields_batch_reuse");
 }
 
 int64_t lzq_sweep_grid_reuse_workspace(const lzq_axis* axes, int32_t n_axes, int32_t n_y) {
@@ -917,11 +926,13 @@ int64_t lzq_sweep_grid_reuse_workspace(const lzq_axis* axes, int32_t n_axes, int
 
 // lzq_sweep_grid_reuse in its two halves: build every z-sum table of the grid (parts & 1) and
 // integrate [start, start + count) from them (parts & 2).
-static int sweep_grid_reuse_parts(const lzq_point* base, const lzq_axis* axes, int32_t n_axes, int64_t start,
-                                  int64_t count, int32_t n_y, int32_t nz, double z_max, const double* d_P,
-                                  double* d_work, int64_t work_doubles, lzq_yield* d_out, void* stream, int parts,
-                                  const char* fn, bool window_axes = false, const lzq_window* base_win = nullptr,
-                                  const lzq_window_tables* d_tables = nullptr) {
+// (cont: the *_cont twins, the tables on the continuum node rule -- lzq_internal.h)
+}  // extern "C"
+int lzq::sweep_grid_reuse_parts(const lzq_point* base, const lzq_axis* axes, int32_t n_axes, int64_t start,
+                                int64_t count, int32_t n_y, int32_t nz, double z_max, const double* d_P,
+                                double* d_work, int64_t work_doubles, lzq_yield* d_out, void* stream, int parts,
+                                const char* fn, bool window_axes, const lzq_window* base_win,
+                                const lzq_window_tables* d_tables, bool cont) {
   lzq::GridSpec gs;
   int rc = make_grid(base, axes, n_axes, start, count, d_out, fn, gs, window_axes);
   if (rc) return rc;
@@ -940,7 +951,7 @@ static int sweep_grid_reuse_parts(const lzq_point* base, const lzq_axis* axes, i
   if (!(parts & 1) && count == 0) return LZQ_OK;
   int dev;
   DevZGrid g;
-  rc = zgrid_for(nz, z_max, g, &dev);
+  rc = zgrid_for(nz, z_max, g, &dev, cont);
   if (rc) return rc;
   const int64_t n_tab = ztable_count(gs);
   int64_t ts = 1;
@@ -953,9 +964,14 @@ static int sweep_grid_reuse_parts(const lzq_point* base, const lzq_axis* axes, i
   const int64_t nbt = blocks_for(n_tab, lzq::kWavesPerBlock), nb = blocks_for(count, lzq::kWavesPerBlock);
   if (nbt > kMaxGrid || nb > kMaxGrid) return fail(LZQ_EINVAL, "%s: too large for one launch", fn);
   if (parts & 1) {
-    // the tables use the exact-underflow truncation: bit-identical to the dense sums
-    const int trunc = g.monotone ? 1 : 0;
-    if (g_exp_variant == lzq::kExpTable)
+    // the tables use the exact-underflow truncation: bit-identical to the dense sums.  A continuum
+    // grid: the live-range kernel (lzq_cont.hip), or with LZQ_TUNE_CONT_SKIP = 0 every node here
+    const int trunc = cont ? 0 : (g.monotone ? 1 : 0);
+    if (cont && lzq::g_cont_skip) {
+      rc = lzq::launch_cont_ztables(g_exp_variant, base, &gs, nullptr, nullptr, n_tab, n_y, stride, g.zt, g.nzp,
+                                    g.key.z_max, exp_table(dev), d_work, (hipStream_t)stream);
+      if (rc) return rc;
+    } else if (g_exp_variant == lzq::kExpTable)
       hipLaunchKernelGGL((lzq::grid_ztable_kernel<lzq::kExpTable>), dim3((unsigned)nbt), dim3(lzq::kBlock), 0,
                          (hipStream_t)stream, *base, gs, n_tab, n_y, stride, g.zt, g.nzp, g.key, exp_table(dev), d_work,
                          trunc);
@@ -974,6 +990,16 @@ static int sweep_grid_reuse_parts(const lzq_point* base, const lzq_axis* axes, i
     LZQ_HIP(hipGetLastError());
   }
   return LZQ_OK;
+}
+extern "C" {
+
+static int sweep_grid_reuse_parts(const lzq_point* base, const lzq_axis* axes, int32_t n_axes, int64_t start,
+                                  int64_t count, int32_t n_y, int32_t nz, double z_max, const double* d_P,
+                                  double* d_work, int64_t work_doubles, lzq_yield* d_out, void* stream, int parts,
+                                  const char* fn, bool window_axes = false, const lzq_window* base_win = nullptr,
+                                  const lzq_window_tables* d_tables = nullptr) {
+  return lzq::sweep_grid_reuse_parts(base, axes, n_axes, start, count, n_y, nz, z_max, d_P, d_work, work_doubles, d_out,
+                                     stream, parts, fn, window_axes, base_win, d_tables, false);
 }
 
 int lzq_sweep_grid_reuse(const lzq_point* base, const lzq_axis* axes, int32_t n_axes, int64_t start, int64_t count,
@@ -1047,11 +1073,13 @@ int lzq_sweep_grid_from_ztables_window(const lzq_point* base, const lzq_window* 
 }
 
 // lzq_sweep_grid_from_ztables[_window]'s checks and table strides, then the solve kernel (lzq_solve.hip)
-int lzq_sweep_grid_solve(const lzq_point* base, const lzq_window* base_win, const lzq_axis* axes, int32_t n_axes,
-                         const lzq_solve* solve, int64_t start, int64_t count, int32_t n_y, int32_t nz, double z_max,
-                         const double* d_P, const double* d_work, int64_t work_doubles,
-                         const lzq_window_tables* d_tables, lzq_yield* d_out, lzq_solve_result* d_sol, void* stream) {
-  const char* fn = "lzq_sweep_grid_solve";
+// (cont: lzq_sweep_grid_solve_cont -- lzq_internal.h)
+}  // extern "C"
+int lzq::sweep_grid_solve(const lzq_point* base, const lzq_window* base_win, const lzq_axis* axes, int32_t n_axes,
+                          const lzq_solve* solve, int64_t start, int64_t count, int32_t n_y, int32_t nz, double z_max,
+                          const double* d_P, const double* d_work, int64_t work_doubles,
+                          const lzq_window_tables* d_tables, lzq_yield* d_out, lzq_solve_result* d_sol, void* stream,
+                          bool cont, const char* fn) {
   if (!solve || (count > 0 && !d_sol)) return fail(LZQ_EINVAL, "%s: bad arguments", fn);
   int rc = lzq_solve_check_host(solve, base_win, axes, n_axes);
   if (rc) return rc;
@@ -1074,7 +1102,7 @@ int lzq_sweep_grid_solve(const lzq_point* base, const lzq_window* base_win, cons
   if (count == 0) return LZQ_OK;
   int dev;
   DevZGrid g;
-  rc = zgrid_for(nz, z_max, g, &dev);
+  rc = zgrid_for(nz, z_max, g, &dev, cont);
   if (rc) return rc;
   int64_t ts = 1;
   for (int a = gs.n_axes - 1; a >= 0; --a)
@@ -1086,6 +1114,15 @@ int lzq_sweep_grid_solve(const lzq_point* base, const lzq_window* base_win, cons
   if (blocks_for(count, lzq::kWavesPerBlock) > kMaxGrid) return fail(LZQ_EINVAL, "%s: too large for one launch", fn);
   return lzq::launch_grid_solve(*base, base_win, gs, wt, *solve, start, count, n_y, d_P, g.key.nz, g.key.z_max,
                                 d_work, stride, d_out, d_sol, (hipStream_t)stream);
+}
+extern "C" {
+
+int lzq_sweep_grid_solve(const lzq_point* base, const lzq_window* base_win, const lzq_axis* axes, int32_t n_axes,
+                         const lzq_solve* solve, int64_t start, int64_t count, int32_t n_y, int32_t nz, double z_max,
+                         const double* d_P, const double* d_work, int64_t work_doubles,
+                         const lzq_window_tables* d_tables, lzq_yield* d_out, lzq_solve_result* d_sol, void* stream) {
+  return lzq::sweep_grid_solve(base, base_win, axes, n_axes, solve, start, count, n_y, nz, z_max, d_P, d_work,
+                               work_doubles, d_tables, d_out, d_sol, stream, false, "lzq_sweep_grid_solve");
 }
 
 int lzq_p_closed_form(const double* d_lambda, int64_t n, double* d_P, void* stream) {

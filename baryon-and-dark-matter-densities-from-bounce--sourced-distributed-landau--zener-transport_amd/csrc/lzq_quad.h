@@ -1173,4 +1173,29 @@ __device__ __forceinline__ double grid_point(const lzq_point& base, const GridSp
   return p.P_chi_to_B;
 }
 
+// ---------------------------------------------------------------------------------------
+// z-sum tables (lzq_sweep_grid_reuse; the kernels are lzq_kernels.hip's and lzq_cont.hip's)
+// ---------------------------------------------------------------------------------------
+constexpr int kTabHdr = 6;
+static_assert(kTabHdr == LZQ_REUSE_TABLE_HEADER, "include/lzq.h");
+
+// The z grid a table is made for, as its header stores it.
+struct ZKey {
+  double nz, z_max;
+};
+
+__device__ __forceinline__ int64_t table_of(const GridSpec& g, int64_t idx) {
+  int64_t t = 0;
+  for (int a = 0; a < g.n_axes; ++a) t += ((idx / g.stride[a]) % g.n[a]) * g.tstride[a];
+  return t;
+}
+
+// flat grid index of table t's representative (every other axis at its first value)
+__device__ __forceinline__ int64_t table_rep(const GridSpec& g, int64_t t) {
+  int64_t idx = 0;
+  for (int a = 0; a < g.n_axes; ++a)
+    if (g.tstride[a]) idx += ((t / g.tstride[a]) % g.n[a]) * g.stride[a];
+  return idx;
+}
+
 }  // namespace lzq

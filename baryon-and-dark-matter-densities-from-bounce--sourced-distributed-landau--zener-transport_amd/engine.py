@@ -96,6 +96,16 @@ class Engine:
             self._check(prev)
         return bool(prev)
 
+    def tune_cont_skip(self, on: bool) -> bool:
+        """The continuum z rule's z-sum tables from the live-range kernel (on, the default) or at every
+        node from the linspace grids' table kernel (include/lzq.h LZQ_TUNE_CONT_SKIP; bit-identical
+        tables either way).  Returns the previous setting."""
+        prev = self.lib.lzq_tune(_native.TUNE_CONT_SKIP, 1 if on else 0)
+        if prev < 0:
+            self._check(prev)
+        self._ztab_key = None
+        return bool(prev)
+
     # -- helpers -------------------------------------------------------------------------
     def _check(self, rc: int) -> None:
         _native.check(rc, self.lib)
@@ -166,17 +176,26 @@ class Engine:
         return out
 
     # -- fpy:158-165 -----------------------------------------------------------------------
-    def aov(self, kernel, ys, nz: int = _native.LZQ_NZ, z_max: float = _native.LZQ_Z_MAX) -> torch.Tensor:
+    def aov(self, kernel, ys, nz: int = _native.LZQ_NZ, z_max: float = _native.LZQ_Z_MAX,
+            continuum: bool = False) -> torch.Tensor:
         """A_over_V_y at every y for the kernel AoverVKernel(I_p, beta_over_H, T_p, v_w, g_star, z_max, nz)
         (fpy:141-165); kernel: an AoverVKernel, or a Config / fpy-schema dict (the kernel main() builds
-        from it, fpy:197)."""
-        nz, z_max = _native.zgrid(nz, z_max)
+        from it, fpy:197).  continuum: the z-sum on the continuum z rule of z_max in place of the
+        (nz, z_max) grid (include/lzq.h "A/V in the continuum limit"; nz is not read)."""
+        if continuum:
+            z_max = _native.cont_z_max(z_max)
+        else:
+            nz, z_max = _native.zgrid(nz, z_max)
         y = self._f64(ys).reshape(-1)
         out = torch.empty_like(y)
         a = to_ctypes_aov(to_aov(kernel))
         with torch.cuda.device(self.device):
-            self._check(self.lib.lzq_aov_batch(None, ctypes.byref(a), _vp(y), y.numel(), nz, z_max, _vp(out),
-                                               self._stream()))
+            if continuum:
+                self._check(self.lib.lzq_aov_batch_cont(None, ctypes.byref(a), _vp(y), y.numel(), z_max, _vp(out),
+                                                        self._stream()))
+            else:
+                self._check(self.lib.lzq_aov_batch(None, ctypes.byref(a), _vp(y), y.numel(), nz, z_max, _vp(out),
+                                                   self._stream()))
         return out
 
     # -- fpy:222-223 ------------------------------------------------------------------------
@@ -191,7 +210,7 @@ class Engine:
     # -- fpy:231-267 + epilogue ----------------------------------------------------------------
     def yields(self, points, n_y: int = 8000, T_lo=None, T_hi=None, P=None, reuse: bool = False,
                nz: int = _native.LZQ_NZ, z_max: float = _native.LZQ_Z_MAX, aov=None, window=None,
-               window_tables=None) -> torch.Tensor:
+               window_tables=None, continuum: bool = False) -> torch.Tensor:
         """points: POINT_DTYPE numpy array or a device byte tensor from points_to_device.
         Returns (n, 6) float64 device tensor in YIELD_FIELDS order.
         reuse: lzq_yields_batch_reuse -- points equal in _native.ZSUM_KEY share one table of
@@ -204,8 +223,19 @@ class Engine:
         lzq_window; see window_to_device): one block for all points or n records; the points'
         source_shape_sigma_y is then not read.  window_tables: the tabulated profiles of the table kind
         (a window.WindowTables, (u, W), or what window_tables_to_device returned).  The z-sums do not
-        depend on the window, so `reuse` applies as without one.  Not with `aov`."""
-        nz, z_max = _native.zgrid(nz, z_max)
+        depend on the window, so `reuse` applies as without one.  Not with `aov`.
+        continuum: the z-sums on the continuum z rule of z_max (include/lzq.h "A/V in the continuum
+        limit"; nz is not read).  Always through shared z-sum tables, one per distinct _native.ZSUM_KEY
+        (`reuse`'s grouping), in chunks where the tables of a batch exceed REUSE_MAX_BYTES; main()'s
+        window only, and not with `aov`."""
+        if continuum:
+            if aov is not None:
+                raise ValueError("yields: a replaced A/V kernel (aov) together with the continuum z rule is not supported")
+            if T_lo is not None or T_hi is not None:
+                raise ValueError("yields: the continuum z rule runs from shared z-sum tables (main()'s window only)")
+            z_max = _native.cont_z_max(z_max)
+        else:
+            nz, z_max = _native.zgrid(nz, z_max)
         d_pts = points if isinstance(points, torch.Tensor) else self.points_to_device(points)
         n = d_pts.numel() // _native.POINT_DTYPE.itemsize
         d_aov = self.aov_to_device(aov, n)
@@ -221,6 +251,10 @@ class Engine:
         tl = None if T_lo is None else self._f64(T_lo)
         th = None if T_hi is None else self._f64(T_hi)
         Pv = None if P is None else self._f64(P)
+        if continuum:
+            with torch.cuda.device(self.device):
+                self._yields_cont(d_pts, n, int(n_y), z_max, Pv, d_win, d_wt, out)
+            return out
         with torch.cuda.device(self.device):
             groups = table_groups(d_pts, n, _ZSUM_WORDS) if reuse and tl is None and th is None and d_aov is None \
                 else None
@@ -255,11 +289,51 @@ class Engine:
                 self.last_yields_path = "dense"
         return out
 
+    def _yields_cont(self, d_pts, n, n_y, z_max, Pv, d_win, d_wt, out) -> None:
+        """Engine.yields(continuum=True): lzq_yields_batch_cont per chunk of points whose tables fit
+        REUSE_MAX_BYTES (one chunk unless nearly every point has a z-sum key of its own)."""
+        stride = max(n_y, 2000) + _native.REUSE_TABLE_HEADER
+        cap = max(1, REUSE_MAX_BYTES // (stride * 8))
+        psz, wsz = _native.POINT_DTYPE.itemsize, _native.WINDOW_DTYPE.itemsize
+        per_point_win = d_win is not None and d_win.numel() // wsz == n
+
+        def groups_of(pts, m):
+            g = table_groups(pts, m, _ZSUM_WORDS)
+            if g is None:   # one point, or sharing would not pay: a table per point
+                ar = torch.arange(m, dtype=torch.int64, device=self.device)
+                g = (ar, ar)
+            return g
+
+        rep, inv = groups_of(d_pts, n) if n else (None, None)
+        chunks = [(0, n, rep, inv)] if n and rep.numel() <= cap else \
+            [(lo, min(lo + cap, n), None, None) for lo in range(0, n, cap)]
+        self._ztab_key = None   # the grid tables in _zwork are overwritten
+        self.last_yields_path = "tables"
+        self.last_cont_chunks = len(chunks)
+        for lo, hi, rep, inv in chunks:
+            m = hi - lo
+            pts = d_pts if m == n else d_pts.view(-1)[lo * psz:hi * psz]
+            if rep is None:
+                rep, inv = groups_of(pts, m)
+            need = rep.numel() * stride
+            if self._zwork is None or self._zwork.numel() < need:
+                self._zwork = torch.empty(need, dtype=torch.float64, device=self.device)
+            idx = inv.to(torch.int32)
+            win = None
+            if d_win is not None:
+                win = d_win.view(-1)[lo * wsz:hi * wsz] if per_point_win and m != n else d_win
+            self._check(self.lib.lzq_yields_batch_cont(
+                _vp(pts), m, n_y, z_max, _vp(None if Pv is None else Pv.reshape(-1)[lo:hi]), _vp(rep), _vp(idx),
+                rep.numel(), _vp(self._zwork), self._zwork.numel(), _vp(win), d_wt.arg if d_wt is not None else None,
+                _vp(out[lo:hi]), self._stream()))
+            self._keepalive_reuse = (rep, idx, pts, win, d_wt)
+
     # -- grid sweep ----------------------------------------------------------------------------
     def sweep(self, base_cfg, axes: Sequence[tuple], start: int, count: int, n_y: int = 8000,
               out: Optional[torch.Tensor] = None, P: Optional[float] = None,
               P_points: Optional[torch.Tensor] = None, reuse: bool = False, nz: int = _native.LZQ_NZ,
-              z_max: float = _native.LZQ_Z_MAX, window=None, window_tables=None, solve=None):
+              z_max: float = _native.LZQ_Z_MAX, window=None, window_tables=None, solve=None,
+              continuum: bool = False):
         """axes: sequence of (field_name, values) (C order, last fastest); field names are
         the lzq_point double fields or 'delta_LZ' / 'm_mix' / 'dprime'.  P_points: optional
         per-point P override ([count], device), e.g. from lz_propagate (config C5).
@@ -280,8 +354,15 @@ class Engine:
         bracketing root solve on the device.  Returns (records, results): the (count, 6) yield records at
         the solutions and the (count, 6) results in _native.SOLVE_RESULT_FIELDS order.  Always through the
         shared z-sum tables, built once per sweep as with `reuse`; tables beyond REUSE_MAX_BYTES raise
-        (there is no dense solve).  Every host-side refusal raises ValueError before any upload."""
-        nz, z_max = _native.zgrid(nz, z_max)
+        (there is no dense solve).  Every host-side refusal raises ValueError before any upload.
+        continuum: the z-sums on the continuum z rule of z_max (include/lzq.h "A/V in the continuum
+        limit"; nz is not read).  Always through the shared z-sum tables, like a solve: tables beyond
+        REUSE_MAX_BYTES raise (there is no dense continuum path)."""
+        if continuum:
+            z_max = _native.cont_z_max(z_max)
+            reuse = True
+        else:
+            nz, z_max = _native.zgrid(nz, z_max)
         if len(axes) > _native.LZQ_MAX_AXES:
             raise ValueError(f"at most {_native.LZQ_MAX_AXES} sweep axes")
         sv = None
@@ -330,12 +411,15 @@ class Engine:
             if reuse:
                 tkey = (bytes(base), tuple((n, t.cpu().numpy().tobytes() if isinstance(v, torch.Tensor)
                                             else np.asarray(v, dtype=np.float64).tobytes())
-                                           for (n, v), t in zip(axes, dev_vals)), int(n_y), self._exp_variant, nz, z_max)
+                                           for (n, v), t in zip(axes, dev_vals)), int(n_y), self._exp_variant,
+                        "continuum" if continuum else nz, z_max)
                 built = tkey == self._ztab_key
                 why = None if need * 8 <= REUSE_MAX_BYTES else f"{n_tables} z-sum tables exceed REUSE_MAX_BYTES"
                 if why is not None and sv is not None:
                     raise ValueError(f"solve: {why}; the solve runs from the shared tables only")
-                if why is None and not built and not 0 < n_tables <= count and sv is None:
+                if why is not None and continuum:
+                    raise ValueError(f"continuum: {why}; the continuum z rule runs from the shared tables only")
+                if why is None and not built and not 0 < n_tables <= count and sv is None and not continuum:
                     why = f"{n_tables} z-sum tables for a chunk of {count} points"
                 if why:
                     _log.warning("lzq reuse_zsums: dense path (same bits): %s", why)
@@ -356,19 +440,35 @@ class Engine:
                         t_arr, t_n = (_native.LzqAxis * max(1, len(keep)))(), len(keep)
                         for k, a in enumerate(keep):
                             t_arr[k].field, t_arr[k].n, t_arr[k].values = arr[a].field, arr[a].n, arr[a].values
-                    self._check(ztables(ctypes.byref(base), t_arr, t_n, int(n_y), nz, z_max, _vp(self._zwork),
-                                        self._zwork.numel(), self._stream()))
+                    if continuum:   # (one entry point: it skips the window axes, like the _window twin)
+                        self._check(self.lib.lzq_sweep_grid_ztables_cont(
+                            ctypes.byref(base), t_arr, t_n, int(n_y), z_max, _vp(self._zwork), self._zwork.numel(),
+                            self._stream()))
+                    else:
+                        self._check(ztables(ctypes.byref(base), t_arr, t_n, int(n_y), nz, z_max, _vp(self._zwork),
+                                            self._zwork.numel(), self._stream()))
                     self._ztab_key = tkey
+                b_win = ctypes.byref(win) if win is not None else None
+                a_wt = d_wt.arg if d_wt is not None else None
                 if sv is not None:
                     sol = torch.empty((count, 6), dtype=torch.float64, device=self.device)
-                    self._check(self.lib.lzq_sweep_grid_solve(
-                        ctypes.byref(base), ctypes.byref(win) if win is not None else None, arr, len(axes),
-                        ctypes.byref(sv), int(start), int(count), int(n_y), nz, z_max, _vp(Pp), _vp(self._zwork),
-                        self._zwork.numel(), d_wt.arg if d_wt is not None else None, _vp(out), _vp(sol),
-                        self._stream()))
+                    if continuum:
+                        self._check(self.lib.lzq_sweep_grid_solve_cont(
+                            ctypes.byref(base), b_win, arr, len(axes), ctypes.byref(sv), int(start), int(count),
+                            int(n_y), z_max, _vp(Pp), _vp(self._zwork), self._zwork.numel(), a_wt, _vp(out), _vp(sol),
+                            self._stream()))
+                    else:
+                        self._check(self.lib.lzq_sweep_grid_solve(
+                            ctypes.byref(base), b_win, arr, len(axes), ctypes.byref(sv), int(start), int(count),
+                            int(n_y), nz, z_max, _vp(Pp), _vp(self._zwork), self._zwork.numel(), a_wt, _vp(out),
+                            _vp(sol), self._stream()))
                     self._keepalive = (dev_vals, d_wt)
                     return out, sol
-                if win is None:
+                if continuum:
+                    self._check(self.lib.lzq_sweep_grid_from_ztables_cont(
+                        ctypes.byref(base), b_win, arr, len(axes), int(start), int(count), int(n_y), z_max, _vp(Pp),
+                        _vp(self._zwork), self._zwork.numel(), a_wt, _vp(out), self._stream()))
+                elif win is None:
                     self._check(self.lib.lzq_sweep_grid_from_ztables(
                         ctypes.byref(base), arr, len(axes), int(start), int(count), int(n_y), nz, z_max, _vp(Pp),
                         _vp(self._zwork), self._zwork.numel(), _vp(out), self._stream()))
@@ -387,11 +487,11 @@ class Engine:
         return out
 
     def solve_point(self, cfg, solve, window=None, window_tables=None, n_y: int = 8000, P: Optional[float] = None,
-                    nz: int = _native.LZQ_NZ, z_max: float = _native.LZQ_Z_MAX):
+                    nz: int = _native.LZQ_NZ, z_max: float = _native.LZQ_Z_MAX, continuum: bool = False):
         """The solve of one configuration: sweep(..., solve=solve) on a grid with no axes.  Returns
         (record, result), two float64[6] device tensors."""
         rec, sol = self.sweep(cfg, [], 0, 1, n_y=n_y, P=P, nz=nz, z_max=z_max, window=window,
-                              window_tables=window_tables, solve=solve)
+                              window_tables=window_tables, solve=solve, continuum=continuum)
         return rec[0], sol[0]
 
     # -- sweep fits, posteriors, observables, ranked points (lzq_fit_*, lzq_post_*, lzq_obs_*,
@@ -515,7 +615,8 @@ class Engine:
 
     def ode(self, points, ode_params, max_steps: Optional[int] = None, chunk: int = 1 << 18,
             share_tables: bool = True, method: str = "radau", group_waves: bool = True, nz: int = _native.LZQ_NZ,
-            z_max: float = _native.LZQ_Z_MAX, aov=None, time_parallel: Optional[bool] = None, window=None) -> tuple:
+            z_max: float = _native.LZQ_Z_MAX, aov=None, time_parallel: Optional[bool] = None, window=None,
+            continuum: bool = False) -> tuple:
         """fpy:385-417 for n points (POINT_DTYPE records + ODE_DTYPE records, as numpy arrays or
         as device byte tensors from points_to_device / ode_params_to_device): (n, 6) yields
         table and (n,) int32 status (enum lzq_ode_status), both on the device.  Points are
@@ -547,7 +648,11 @@ class Engine:
         Radau only.  self.last_ode_tp_iters: the Newton updates per point of the last
         time-parallel call (<= 0: integrated sequentially).
         window: must be None -- the ODE path's source term keeps the reference's Gaussian window
-        (include/lzq.h); any other raises."""
+        (include/lzq.h); any other raises.
+        continuum: must be False -- the ODE spline tables stay on the linspace z grids."""
+        if continuum:
+            raise NotImplementedError("Engine.ode does not take the continuum z rule: the ODE spline tables "
+                                      "(lzq_ode_tables) are built on the linspace z grids only")
         if window is not None:
             raise NotImplementedError("Engine.ode takes no window: the ODE entry points integrate the reference's "
                                       "Gaussian window (fpy:226-228); use Engine.yields(window=...)")

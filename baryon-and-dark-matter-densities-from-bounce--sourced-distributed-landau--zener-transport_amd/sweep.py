@@ -190,6 +190,13 @@ class SweepSpec:
     # the inverse sweep (solve.py): one parameter per grid point solved for a target yield; the table
     # then holds the records at the solutions and solve.npy the results
     solve: Optional[dict] = None
+    # "linspace": the reference's (nz, z_max) grid; "continuum": the converged z-integral on the
+    # continuum z rule of z_max (include/lzq.h "A/V in the continuum limit"; nz is then not read)
+    z_rule: str = "linspace"
+
+    @property
+    def continuum(self) -> bool:
+        return self.z_rule == "continuum"
 
     @property
     def total(self) -> int:
@@ -223,6 +230,8 @@ class SweepSpec:
             d["window"] = self.window.to_json()
         if self.solve is not None:
             d["solve"] = _solve.normalize(self.solve)
+        if self.z_rule != "linspace":
+            d["z_rule"] = self.z_rule
         return d
 
     def axis_values(self, start: int, count: int, device) -> dict:
@@ -371,10 +380,24 @@ def spec_from_json(d: dict) -> SweepSpec:
     # 0 means "no cap", as --ode-max-steps 0 on the command line does (one meaning in both places)
     spec = SweepSpec(d.get("name", "custom"), base, axes, int(d.get("n_y", 8000)), d.get("notes", ""), cr, method, prof,
                      nz, z_max, None if ms is None or int(ms) == 0 else int(ms), win,
-                     _solve.normalize(d["solve"]) if d.get("solve") else None)
+                     _solve.normalize(d["solve"]) if d.get("solve") else None, d.get("z_rule", "linspace"))
+    check_z_rule(spec)
     check_window_spec(spec)
     check_solve_spec(spec)
     return spec
+
+
+def check_z_rule(spec: SweepSpec) -> None:
+    """A "z_rule" the sweep cannot run, as a ValueError: an unknown rule, a z_max the continuum rule
+    refuses, or the continuum rule on a spec whose points take the ODE fallback (the ODE spline tables
+    stay on the linspace grids)."""
+    if spec.z_rule not in ("linspace", "continuum"):
+        raise ValueError(f"z_rule must be 'linspace' or 'continuum', got {spec.z_rule!r}")
+    if spec.continuum:
+        _native.cont_z_max(spec.z_max)
+        if is_ode_spec(spec):
+            raise ValueError("z_rule 'continuum' on a spec whose points take the ODE fallback (sigma_v / Gamma_wash / "
+                             "depletion): the ODE spline tables are built on the linspace z grids only")
 
 
 def check_solve_spec(spec: SweepSpec) -> None:
@@ -874,6 +897,7 @@ def make_compute(spec: SweepSpec, engine, reuse: bool = False, window_host_recor
     window_host_records: a window spec through explicit host-built records even where the grid
     entry points would take it (the same bits; tools/bench_window.py's baseline)."""
     pcache = {}   # the profile's device splines, built once per sweep
+    check_z_rule(spec)
     check_window_spec(spec)
     check_solve_spec(spec)
     if spec.solve is not None:
@@ -888,7 +912,7 @@ def make_compute(spec: SweepSpec, engine, reuse: bool = False, window_host_recor
             _, compute_solve.solve_last = engine.sweep(
                 spec.base, grid_axes_for_kernel(spec), s, n, n_y=spec.n_y, out=out, P_points=P_points, nz=spec.nz,
                 z_max=spec.z_max, window=None if spec.window is None else spec.window.block, window_tables=d_tables,
-                solve=spec.solve)
+                solve=spec.solve, continuum=spec.continuum)
         compute_solve.solve = _solve.normalize(spec.solve)
         compute_solve.solve_last = compute_solve.solve_local = None
         return compute_solve
@@ -905,7 +929,7 @@ def make_compute(spec: SweepSpec, engine, reuse: bool = False, window_host_recor
                     P_points = profile_P(spec, s, n, engine, pcache)   # the per-point override
                 engine.sweep(spec.base, grid_axes_for_kernel(spec), s, n, n_y=spec.n_y, out=out, P_points=P_points,
                              reuse=reuse, nz=spec.nz, z_max=spec.z_max, window=spec.window.block,
-                             window_tables=d_tables)
+                             window_tables=d_tables, continuum=spec.continuum)
             return compute_window_grid
 
         # two axes write one field of the block (the entry points refuse that): explicit point
@@ -918,7 +942,8 @@ def make_compute(spec: SweepSpec, engine, reuse: bool = False, window_host_recor
             if spec.profile is not None:
                 P_points = profile_P(spec, s, n, engine, pcache)   # the per-point override
             out.copy_(engine.yields(pts, n_y=spec.n_y, P=P_points, reuse=reuse, nz=spec.nz, z_max=spec.z_max,
-                                    window=window_records(spec, s, n), window_tables=d_tables))
+                                    window=window_records(spec, s, n), window_tables=d_tables,
+                                    continuum=spec.continuum))
             engine.last_reuse = engine.last_yields_path
         return compute_window
     if is_ode_spec(spec):
@@ -967,7 +992,7 @@ def make_compute(spec: SweepSpec, engine, reuse: bool = False, window_host_recor
         if spec.profile is not None:
             P_points = profile_P(spec, s, n, engine, pcache)
         engine.sweep(spec.base, grid_axes_for_kernel(spec), s, n, n_y=spec.n_y, out=out, P_points=P_points,
-                     reuse=reuse, nz=spec.nz, z_max=spec.z_max)
+                     reuse=reuse, nz=spec.nz, z_max=spec.z_max, continuum=spec.continuum)
     return compute
 
 
@@ -985,6 +1010,9 @@ def main(argv=None):
                          "(lzq_sweep_grid_reuse: bit-identical, much faster; not the dense headline mode)")
     ap.add_argument("--nz", type=int, default=None, help="z nodes of the A/V kernel (AoverVKernel nz, fpy:142)")
     ap.add_argument("--z-max", type=float, default=None, help="z_max of the A/V kernel (fpy:142)")
+    ap.add_argument("--continuum", action="store_true",
+                    help="the A/V z-sum as a converged z-integral on the continuum z rule of z_max in place of the "
+                         "(nz, z_max) grid (a spec file's \"z_rule\": \"continuum\"); always through shared z-sum tables")
     ap.add_argument("--ode-max-steps", type=int, default=None,
                     help=f"cap on one ODE point's Radau steps (default {ODE_MAX_STEPS}; 0 = no cap)")
     ap.add_argument("--dist-backend", default="nccl",
@@ -1020,6 +1048,9 @@ def main(argv=None):
     if args.nz is not None or args.z_max is not None:
         spec.nz, spec.z_max = _native.zgrid(spec.nz if args.nz is None else args.nz,
                                             spec.z_max if args.z_max is None else args.z_max)
+    if args.continuum:
+        spec.z_rule = "continuum"
+    check_z_rule(spec)
     if args.ode_max_steps is not None:
         spec.ode_max_steps = None if args.ode_max_steps == 0 else args.ode_max_steps
     if args.solve is not None:

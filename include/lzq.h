@@ -182,8 +182,14 @@ int lzq_ztables(int32_t nz, double z_max, double* z, double* gamma4, double* ome
  * wavefront per table; bit 1: the spline's per-knot work over a wavefront's lanes around its two
  * recurrences instead of one lane per table.  The tables are bit-identical either way
  * (tests/test_gpu_ode_tp.py). */
+/* LZQ_TUNE_CONT_SKIP (1 = on, the default; 0 = off): the z-sum tables of the continuum z rule (the
+ * *_cont entry points below) from the live-range kernel -- one wavefront per (table, 64 y-nodes), each
+ * stopping at the first node beyond which every lane's term underflows -- or, off, from the table
+ * kernel of the linspace grids at every node.  The tables are bit-identical either way
+ * (tests/test_gpu_cont.py). */
 enum lzq_tune_key { LZQ_TUNE_EXP = 0, LZQ_TUNE_TRUNCATE = 1, LZQ_TUNE_ODE_COOP = 2, LZQ_TUNE_ODE_LAUNCH_STEPS = 3,
-                    LZQ_TUNE_PROFILE_FLAT = 4, LZQ_TUNE_ODE_TP_INTERVAL = 5, LZQ_TUNE_ODE_TABLE_WIDE = 6 };
+                    LZQ_TUNE_PROFILE_FLAT = 4, LZQ_TUNE_ODE_TP_INTERVAL = 5, LZQ_TUNE_ODE_TABLE_WIDE = 6,
+                    LZQ_TUNE_CONT_SKIP = 7 };
 enum lzq_exp_variant { LZQ_EXP_POLY11 = 0, LZQ_EXP_TABLE = 1 };
 int lzq_tune(int32_t key, int32_t value);
 
@@ -419,8 +425,64 @@ int lzq_sweep_grid_solve(const lzq_point* base, const lzq_window* base_win /* NU
 /* The solve's host-side refusals (all of the above but d_P's).  Axis values are not read.  No GPU. */
 int lzq_solve_check_host(const lzq_solve* solve, const lzq_window* base_win, const lzq_axis* axes, int32_t n_axes);
 
+/* ---- A/V in the continuum limit of the z grid --------------------------- */
+/* Every yield above inherits the reference's z grid -- linspace(0, z_max, nz), trapezoid weights, the
+ * cancelling gamma4 of fpy:156 -- in which Y_B is not converged, and no finer linspace
+ * grid reaches the limit (see lzq_init).  The entry points below replace the z-sum alone by a
+ * converged z-integral on a fixed node rule of their own (csrc/lzq_cont.h holds the one definition
+ * that the host and the device build):
+ *
+ *   A/V_cont(y) = 0 for y > 50, else pref0 e^yh F_cont(c),  yh = clip(y, +-50), c = -(I_p/6) e^yh
+ *   F_cont(c)   = sum_k omega_k exp(c gamma4_k)   over the rule's nodes, ascending in z
+ *   omega_k     = z_k^2 e^{-z_k} w_k,  gamma4_k = gamma(4, z_k) without the cancellation of fpy:156
+ *
+ * pref0, the clip, the y > 50 zero and everything outside the z-integral stay the reference's
+ * (fpy:158-165, 231-267).  The rule: 20-point Gauss-Legendre on panels geometric in z (edges
+ * z_max 2^-j down to the first at or below 1e-6, plus the panel from 0); z_max = 30 gives 520 nodes and
+ * a rule error of 1.7e-16 relative, below the inner loop's exponential.  z_max stays a parameter; there
+ * is no nz.  z_max not finite or <= 0 is LZQ_EINVAL (as is one so small that the first node's weight
+ * leaves the inner loop's range, z_max below ~1e-49).  An opt-in mode: no default changes.
+ *
+ * The yields always go through shared z-sum tables (lzq_sweep_grid_reuse's format).  A continuum
+ * table's header carries a z grid no linspace grid can have (nz slot -1, z_max slot z_max), so a
+ * linspace entry point given a continuum table, or the reverse, returns NaN yields.  The tables come
+ * from the live-range kernel (LZQ_TUNE_CONT_SKIP); the integration, window and solve kernels are the
+ * linspace grids'.  Each entry point is its namesake without the _cont suffix less the nz argument;
+ * base_win / d_win / d_tables are optional (NULL: the point's Gaussian), and with a window the axes
+ * may carry the window fields (the table half skips them). */
+/* Host copies of the rule's tables for z_max: *n nodes (set whenever non-NULL), ascending in
+ * (0, z_max); z, gamma4, omega may be NULL (call once for *n, then with arrays of *n doubles).  No GPU. */
+int lzq_cont_tables(double z_max, double* z, double* gamma4, double* omega, int32_t* n);
+/* The host build of the definition: out[i] = A/V_cont(y[i]) for the kernel of aov (else of *pt, as
+ * lzq_aov_batch), a plain left-to-right FP64 sum with libm's exp.  No GPU. */
+int lzq_aov_cont_host(const lzq_point* pt, const lzq_aov_params* aov, const double* y, int64_t n, double z_max,
+                      double* out);
+int lzq_aov_batch_cont(const lzq_point* pt, const lzq_aov_params* aov, const double* d_y, int64_t n, double z_max,
+                       double* d_out, void* stream);
+int lzq_sweep_grid_ztables_cont(const lzq_point* base, const lzq_axis* axes, int32_t n_axes, int32_t n_y, double z_max,
+                                double* d_work, int64_t work_doubles, void* stream);
+int lzq_sweep_grid_from_ztables_cont(const lzq_point* base, const lzq_window* base_win, const lzq_axis* axes,
+                                     int32_t n_axes, int64_t start, int64_t count, int32_t n_y, double z_max,
+                                     const double* d_P, const double* d_work, int64_t work_doubles,
+                                     const lzq_window_tables* d_tables, lzq_yield* d_out, void* stream);
+/* both halves in one call (an empty range validates only) */
+int lzq_sweep_grid_cont(const lzq_point* base, const lzq_window* base_win, const lzq_axis* axes, int32_t n_axes,
+                        int64_t start, int64_t count, int32_t n_y, double z_max, const double* d_P, double* d_work,
+                        int64_t work_doubles, const lzq_window_tables* d_tables, lzq_yield* d_out, void* stream);
+/* explicit points, as lzq_yields_batch_reuse[_window] */
+int lzq_yields_batch_cont(const lzq_point* d_points, int64_t n, int32_t n_y, double z_max, const double* d_P,
+                          const int64_t* d_rep, const int32_t* d_table_index, int64_t n_tables, double* d_work,
+                          int64_t work_doubles, const lzq_window* d_win, const lzq_window_tables* d_tables,
+                          lzq_yield* d_out, void* stream);
+int lzq_sweep_grid_solve_cont(const lzq_point* base, const lzq_window* base_win, const lzq_axis* axes, int32_t n_axes,
+                              const lzq_solve* solve, int64_t start, int64_t count, int32_t n_y, double z_max,
+                              const double* d_P, const double* d_work, int64_t work_doubles,
+                              const lzq_window_tables* d_tables, lzq_yield* d_out, lzq_solve_result* d_sol,
+                              void* stream);
+
 /* The ODE entry points below take no window: their source term keeps the reference's Gaussian
- * (fpy:226-228).  Engine.ode and the facade's ODE operators raise when given another one. */
+ * (fpy:226-228).  Engine.ode and the facade's ODE operators raise when given another one.  Nor do they
+ * take the continuum rule: lzq_ode_tables stays on the linspace grids. */
 
 /* ---- ODE fallback (fpy:200-219, 270-286, 385-417) -------------------------------------- */
 /* Configurations with sigma_v != 0, Gamma_wash != 0 or depletion leave the fast path
