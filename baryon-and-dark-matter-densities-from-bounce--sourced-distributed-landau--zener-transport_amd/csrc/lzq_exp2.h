@@ -321,6 +321,16 @@ LZQ_HD double seg_node_zero(double c2N, double g, double Av, double Ts) {
 // a VGPR copy of it was kept live across the y-loop, at the cost of a spill.)
 LZQ_HD double seg_node_dead(double Av, double Ts) { return Ts * fma_vvs(Av, Av, kSqBeta); }
 
+// A clamped pass that holds dead lanes (LZQ_PASS_LEAN; zsum_dispatch's last branch, zsum_uniform_lane in
+// lzq_quad.h).  A dead lane runs with c2N = +0.0: t = M at every node, so it never passes seg_clamped,
+// and its clamped magic sum max(M, M + KMIN) is the constant M.  From the first node at which every
+// live lane is clamped, every lane reads one entry of its own at every node -- the uniform-entry
+// argument with the entry held per lane: T''[0] with nothing inserted for a dead lane (seg_entry on
+// M), the entry of M + KMIN for the others.  `dead` does not depend on the node, so the test stays
+// monotone in k.
+LZQ_HD bool seg_clamped_or_dead(bool dead, double c2N, double g, double Mv) { return dead || seg_clamped(c2N, g, Mv); }
+LZQ_HD double seg_entry_lane(const double* tabp, bool dead) { return seg_entry(tabp, dead ? kTabMagic : kTabTClamp); }
+
 // Frozen stretches.  gamma4 saturates, so g4_k moves ever less with k, and a lane's rounded
 // intermediate -- s = fma(c2N, g, A) on a zero pass, t = fma(c2N, g, M) on a clamp-free one -- stops
 // changing long before the pass ends (on small |c2N| it never changes).  Both are correctly rounded

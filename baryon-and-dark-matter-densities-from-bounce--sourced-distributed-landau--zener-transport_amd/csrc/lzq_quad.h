@@ -11,6 +11,7 @@
 #include "../../include/lzq.h"
 #include "lzq_exp2.h"
 #include "lzq_physics.h"
+#include "lzq_ynode.h"
 
 // linkage of the header's __constant__ tables: external in lzq_kernels.hip (the headline's code
 // object is unchanged by the split), internal in any other translation unit that includes it
@@ -103,6 +104,41 @@ constexpr int kFrozenSeg = (LZQ_UNIFORM_SEG != 0 && LZQ_ZERO_SEG != 0 && LZQ_DEA
 static_assert(LZQ_GROUP_SEG == 0 || LZQ_GROUP_SEG == 2 || LZQ_GROUP_SEG == 4, "LZQ_GROUP_SEG is 0, 2 or 4");
 constexpr int kGroupSeg =
     (kFrozenSeg >= 1 && LZQ_ACC_LDS != 0 && LZQ_Y_RECOMPUTE != 0 && LZQ_YFACT_EARLY == 0) ? LZQ_GROUP_SEG : 0;
+// the once-per-pass work of the dense y-loop without what the result does not need (yb_wave, yb_group,
+// zsum_dispatch):
+//   * y, e^y and the trapezoid weight stay live from the pre-loop code to the integration on every pass
+//     that does not enter the table-lookup loop zsum<> (which needs ~60 of the 64 VGPRs); a pass that
+//     does re-forms them on its own branch, as every pass did before;
+//   * e^y takes its [-50, 50] clamp as one max and one min (y is a finite linspace element) and an
+//     exp_sc without the range clamp that cannot fire behind it; the Gaussian window, whose argument
+//     is <= 0, keeps the lower clamp only;
+//   * a pass that touches neither end of the y-grid forms y and the weight without the end-of-grid
+//     selects (lzq_ynode.h);
+//   * a clamped pass that holds dead lanes runs its suffix from the batch at which every LIVE lane is
+//     clamped through the six-operation uniform node with the entry held per lane (zsum_uniform_lane).
+// Same operations on the same operands at every node, no node skipped.  0: the code before it.  Needs
+// the default segment paths (LZQ_UNIFORM_SEG, LZQ_ZERO_SEG, LZQ_DEAD_SEG, LZQ_FROZEN_SEG, LZQ_GROUP_SEG)
+// and the default y-loop; the table and reuse modes keep the old pre- and post-loop code.
+// A/B builds: 2 the per-pass work only, 3 the mixed pass only.
+#ifndef LZQ_PASS_LEAN
+#define LZQ_PASS_LEAN 1
+#endif
+static_assert(LZQ_PASS_LEAN >= 0 && LZQ_PASS_LEAN <= 3, "LZQ_PASS_LEAN is 0, 1, 2 or 3");
+constexpr bool kLeanDefaults = LZQ_UNIFORM_SEG == 1 && LZQ_ZERO_SEG == 1 && LZQ_DEAD_SEG == 1 && LZQ_FROZEN_SEG == 2 &&
+                               LZQ_GROUP_SEG == 4 && LZQ_ACC_LDS != 0 && LZQ_Y_RECOMPUTE != 0 && LZQ_YFACT_EARLY == 0;
+constexpr bool kLeanPass = kLeanDefaults && (LZQ_PASS_LEAN == 1 || LZQ_PASS_LEAN == 2);
+// the slots of a group whose y and e^y stay live across its sweep (4, 2 or 0: the others re-form them)
+#ifndef LZQ_PASS_LEAN_KEEP
+#define LZQ_PASS_LEAN_KEEP 4
+#endif
+constexpr int kLeanKeep = LZQ_PASS_LEAN_KEEP;
+// which of y (1), e^y (2) and the weight (4) a single pass keeps live across its lean loops; the others
+// are re-formed after the z-loop on every pass
+#ifndef LZQ_PASS_LEAN_KEEP1
+#define LZQ_PASS_LEAN_KEEP1 7
+#endif
+constexpr int kLeanKeep1 = LZQ_PASS_LEAN_KEEP1;
+constexpr bool kLeanMixed = kLeanDefaults && (LZQ_PASS_LEAN == 1 || LZQ_PASS_LEAN == 3);
 constexpr int kKUnroll = LZQ_KUNROLL;  // z-nodes per scalar-load batch (must divide 1200)
 constexpr int kYB = LZQ_YB;            // y-nodes per lane per pass (independent chains)
 static_assert(kNZ % kKUnroll == 0, "z unroll must divide nz");
@@ -208,12 +244,17 @@ LZQ_QUAD_CONST_LINKAGE __constant__ double kExpC[15] = {
     0x1.1111111111111p-7,  0x1.5555555555555p-5,  0x1.5555555555555p-3,  0x1.0p-1,  // 1/13! .. 1/2!
     0x1.71547652b82fep+0,                                                           // 1/ln2
     0x1.62e42fefa39efp-1,  0x1.abc9e3b39803fp-56};                                  // ln2 hi, lo
+//
+// The argument is clamped to [-1100, 710] first.  A caller that has shown more takes less of the clamp
+// (LZQ_PASS_LEAN): kExpIn for an argument already inside the range, kExpLow for one that is <= 0 or NaN.
+enum ExpClamp { kExpIn = 0, kExpLow = 1, kExpBoth = 3 };
+template <int CLAMP = kExpBoth>
 __device__ __forceinline__ double exp_sc(double x) {
   int o = 0;
   asm volatile("" : "+s"(o));
   const double* c = kExpC + o;
-  x = x < -1100.0 ? -1100.0 : x;  // NaN passes through both
-  x = x > 710.0 ? 710.0 : x;
+  if constexpr ((CLAMP & 1) != 0) x = x < -1100.0 ? -1100.0 : x;  // NaN passes through both
+  if constexpr ((CLAMP & 2) != 0) x = x > 710.0 ? 710.0 : x;
   const double k = __builtin_rint(x * c[12]);
   double r = __builtin_fma(-k, c[13], x);
   r = __builtin_fma(-k, c[14], r);
@@ -227,10 +268,16 @@ __device__ __forceinline__ double exp_sc(double x) {
 
 // numpy.linspace element (handles numpy's step == 0 branch as well)
 __device__ __forceinline__ double y_node(const QuadSetup& s, int j) {  // n_y is int32
-  const int n = (int)s.n;
-  if (j == n - 1) return s.y_hi;
-  if (s.step == 0.0) return ((double)j / (double)(n - 1)) * s.delta + s.y_lo;
-  return (double)j * s.step + s.y_lo;
+  return y_node_general(s, j);
+}
+
+// e^y of the A/V prefactor, fpy:161: exp(clip(y, -50, 50)).  LEAN (LZQ_PASS_LEAN; y is a finite linspace
+// element, never NaN): the clip is one max and one min, and exp_sc runs without the clamp of its own that
+// cannot fire behind it -- the same argument, the same bits.
+template <bool LEAN>
+__device__ __forceinline__ double exp_y(double y) {
+  if constexpr (LEAN) return exp_sc<kExpIn>(__builtin_fmin(__builtin_fmax(y, -50.0), 50.0));
+  else return exp_sc(pymax(pymin(y, 50.0), -50.0));
 }
 
 // Per-y factors of the integrand of fpy:264-265 that do not depend on F, computed BEFORE the
@@ -310,9 +357,11 @@ __device__ __forceinline__ YFactors y_factors(const QuadSetup& s, double y, doub
 }
 
 // fpy:262: the reference's window, exp(-(y/sigma_y)^2 / 2)
+// (LEAN, LZQ_PASS_LEAN: the argument is <= 0 or NaN, so exp_sc's upper clamp cannot fire and is left out)
+template <bool LEAN = false>
 __device__ __forceinline__ double gauss_window(const QuadSetup& s, double y) {
   double q = (LZQ_YFAST & 4) ? y * s.isig : y / s.sig;
-  return exp_sc(-0.5 * (q * q));
+  return exp_sc<LEAN ? kExpLow : kExpBoth>(-0.5 * (q * q));
 }
 
 __device__ __forceinline__ YFactors y_factors(const QuadSetup& s, double y, double expy, double wt) {
@@ -325,6 +374,13 @@ struct SlotGaussWindow {
   static __device__ __forceinline__ double eval(const Slot& slot, double y) { return gauss_window(slot.s, y); }
 };
 
+// Win::eval; the default window in its lean form where LEAN (LZQ_PASS_LEAN)
+template <bool LEAN, typename Win, typename Slot>
+__device__ __forceinline__ double win_eval(const Slot& slot, double y) {
+  if constexpr (LEAN && __is_same(Win, SlotGaussWindow)) return gauss_window<true>(slot.s, y);
+  else return Win::eval(slot, y);
+}
+
 __device__ __forceinline__ double integrand_from(const YFactors& f, double F) {
   double Av = f.live != 0.0 ? f.pexp * F : 0.0;           // fpy:159-165
   double SB = f.PJ * Av * f.W;                            // fpy:264
@@ -333,9 +389,30 @@ __device__ __forceinline__ double integrand_from(const YFactors& f, double F) {
 
 // trapezoid weight of y-node j: (d_{j-1} + d_j)/2 with d = diff(ys)      fpy:267
 __device__ __forceinline__ double y_weight(const QuadSetup& s, int j, double y) {
-  double dl = (j > 0) ? y - y_node(s, j - 1) : 0.0;
-  double dr = (j + 1 < (int)s.n) ? y_node(s, j + 1) - y : 0.0;
-  return 0.5 * (dl + dr);
+  return y_weight_general(s, j, y);
+}
+
+// y, e^y and the trapezoid weight of y-node j of a pass, as yb_wave and yb_group form them.  `interior`
+// (wave-uniform; LZQ_PASS_LEAN only): the pass touches neither end of the y-grid (y_pass_interior,
+// lzq_ynode.h) and takes the forms without the end-of-grid selects; otherwise j may lie past the grid
+// (a tail lane of the last pass), which recomputes the last node with weight 0.
+// WHICH: the values written (kKeepY | kKeepEy | kKeepWt); the others are left as they are.
+constexpr int kKeepY = 1, kKeepEy = 2, kKeepWt = 4;
+template <bool LEAN, int WHICH = 7>
+__device__ __forceinline__ void y_triple(const QuadSetup& s, int j, int n, bool interior, double& y, double& ey,
+                                         double& wt) {
+  double yj;
+  if (LEAN && interior) {
+    yj = y_node_interior(s.y_lo, s.step, j);
+    if constexpr ((WHICH & kKeepWt) != 0) wt = y_weight_interior(s.y_lo, s.step, j, yj);
+  } else {
+    const int jj = j < n ? j : n - 1;
+    yj = y_node(s, jj);
+    if constexpr ((WHICH & kKeepWt) != 0) wt = j < n ? y_weight(s, jj, yj) : 0.0;
+  }
+  if constexpr ((WHICH & kKeepY) != 0) y = yj;
+  // (one copy behind the branch: the code is what a launch fetches from HBM)
+  if constexpr ((WHICH & kKeepEy) != 0) ey = exp_y<LEAN>(yj);
 }
 
 // exp variants of the inner loop (lzq_tune(LZQ_TUNE_EXP, ...))
@@ -514,6 +591,35 @@ __device__ __forceinline__ void zsum_uniform(const ZNode* __restrict__ zt, doubl
   }
 }
 
+// The uniform-entry loop with the entry held per lane (LZQ_PASS_LEAN): nodes kbeg .. kend of a clamped
+// pass that holds dead lanes, from the batch at which every LIVE lane is clamped.  A dead lane runs with
+// c2e = +0.0, so its t is M at every node and max(M, M + KMIN) = M: it reads T''[0] with nothing inserted
+// throughout, while a live lane reads the entry of M + KMIN.  Each lane's clamped magic sum is therefore
+// one constant from kbeg on -- not the same one in every lane -- and Ts[b] is its entry as the general
+// loop forms it (seg_entry on M for a dead lane, on M + KMIN for the others), a VGPR pair.  The node is
+// zsum_uniform's: seg_node's six FP64 operations on the general node's operands, every node executed.
+template <int YB>
+__device__ __forceinline__ void zsum_uniform_lane(const ZNode* __restrict__ zt, const double (&Ts)[YB],
+                                                  const double (&c2)[YB], double (&F)[YB], int kend, int kbeg) {
+  if (kbeg == 0) {
+#pragma unroll
+    for (int b = 0; b < YB; ++b) F[b] = 0.0;
+  }
+  const double Mv = vgpr_const(kTabMagic);
+  for (int k = kbeg; k < kend; k += kKUnroll) {
+    double g4[kKUnroll], om[kKUnroll];
+#pragma unroll
+    for (int kk = 0; kk < kKUnroll; ++kk) {
+      g4[kk] = zt[k + kk].g4;
+      om[kk] = zt[k + kk].omega;
+    }
+#pragma unroll
+    for (int kk = 0; kk < kKUnroll; ++kk)
+#pragma unroll
+      for (int b = 0; b < YB; ++b) F[b] = __builtin_fma(om[kk], seg_node(c2[b], g4[kk], Mv, Ts[b]), F[b]);
+  }
+}
+
 // The all-dead loop (LZQ_DEAD_SEG): a zero pass whose 64 lanes are all dead, so every lane runs with
 // c2e = +0.0.  Then s = fma(+0 * g, A) = A at every node, and q = fma(A, A, beta) and v = T''[0] * q
 // are the same two numbers at each of them (seg_node_dead): they are formed once, and a node is F's
@@ -601,6 +707,19 @@ __device__ __forceinline__ double zero_magic(double Mv) {
   else return kTabMagic;
 }
 
+// __shfl_xor over the 64 lanes with the lane index re-derived where it is used (two v_mbcnt; volatile).
+// __shfl_xor's own is hoisted out of the y-loop and held in a VGPR across every z-loop, which the values
+// the lean passes keep live there have no room for (LZQ_PASS_LEAN).
+__device__ __forceinline__ double shfl_xor_rederived(double v, int off) {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  const int a = (l ^ off) << 2;
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)(uint32_t)b);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)(uint32_t)(b >> 32));
+  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+
 // Pass-level wrapper: "dead" lanes, c2 * g4_1 <= -N*1077 (every node k >= 1 underflows to
 // exactly 0: g4 is increasing and omega_0 = 0), run the loop with c2 = 0 and are zeroed
 // afterwards -- the same instruction stream, the exact zero.
@@ -628,9 +747,19 @@ __device__ __forceinline__ double zero_magic(double Mv) {
 //
 // Returns whether the pass ran as F's accumulate alone from node 0 (all lanes dead, or a zero pass with
 // k3 = 0): what yb_wave's pass grouping (LZQ_GROUP_SEG) takes as its cue to try a group next.
-template <int YB, int EXPV, int NZ = 0>
+//
+// after_general (LZQ_PASS_LEAN; yb_wave's): called at the end of the branches that ran the table-lookup
+// loop zsum<>, and of no other.  What the caller keeps in registers across the lean loops it re-forms
+// there, so that on the control-flow graph those values are dead through zsum<>, which has no room for
+// them (a flag tested after the branches rejoin would keep them live through it).  The default does nothing.
+struct NoAfterGeneral {
+  __device__ __forceinline__ void operator()() const {}
+};
+
+template <int YB, int EXPV, int NZ = 0, typename After = NoAfterGeneral>
 __device__ __forceinline__ bool zsum_dispatch(const ZNode* __restrict__ zt, int nzp, const double* tab,
-                                              const double (&c2)[YB], double (&F)[YB], int truncate = 0) {
+                                              const double (&c2)[YB], double (&F)[YB], int truncate = 0,
+                                              const After& after_general = After()) {
   const int nz = NZ > 0 ? NZ : nzp;
   const double g_1 = zt[1].g4, g_max = zt[nz - 1].g4;
   bool dead[YB], small = true;
@@ -653,7 +782,10 @@ __device__ __forceinline__ bool zsum_dispatch(const ZNode* __restrict__ zt, int 
       thr = pymax(thr, tb);
     }
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) thr = pymax(thr, __shfl_xor(thr, off, kWaveSize));
+    for (int off = 32; off >= 1; off >>= 1) {
+      if constexpr (kLeanPass) thr = pymax(thr, shfl_xor_rederived(thr, off));
+      else thr = pymax(thr, __shfl_xor(thr, off, kWaveSize));
+    }
     thr = uniform(thr);
     // first k with g4_k > thr (g4 increasing): scalar binary search over the z table
     int lo = 0, hi = nz;
@@ -742,17 +874,48 @@ __device__ __forceinline__ bool zsum_dispatch(const ZNode* __restrict__ zt, int 
       } else {
         zsum<YB, EXPV, false>(zt, tab, c2e, F, kend);
       }
+      after_general();
     } else {
-      const int k2 = seg_first_batch(
-          [&](double g) {
-            bool c = true;
+      // Dead lanes among clamped ones (LZQ_PASS_LEAN): a dead lane (c2e = +0.0, t = M) never passes
+      // seg_clamped, but its clamped magic sum is the constant M at every node.  So the search asks for
+      // the first batch at which every LIVE lane is clamped (dead does not depend on k: still monotone;
+      // without dead lanes it is the test it was), and from there a pass that holds dead lanes runs the
+      // uniform node with each lane's own entry, the others with the one entry in SGPRs as before.
+      if constexpr (kLeanMixed) {
+        bool any_dead = false;
 #pragma unroll
-            for (int b = 0; b < YB; ++b) c = c && seg_clamped(c2e[b], g, Mv);
-            return __all(c) != 0;
-          },
-          [&](int k) { return zt[k].g4; }, kend, kKUnroll);
-      if (k2 > 0) zsum<YB, EXPV, true>(zt, tab, c2e, F, k2);
-      zsum_uniform<YB>(zt, uniform(seg_entry(tab, kTabTClamp)), c2e, F, kend, k2);
+        for (int b = 0; b < YB; ++b) any_dead = any_dead || dead[b];
+        const bool mixed = __any(any_dead) != 0;  // wave-uniform
+        const int k2 = seg_first_batch(
+            [&](double g) {
+              bool c = true;
+#pragma unroll
+              for (int b = 0; b < YB; ++b) c = c && seg_clamped_or_dead(dead[b], c2e[b], g, Mv);
+              return __all(c) != 0;
+            },
+            [&](int k) { return zt[k].g4; }, kend, kKUnroll);
+        if (k2 > 0) zsum<YB, EXPV, true>(zt, tab, c2e, F, k2);
+        if (mixed) {
+          double Tl[YB];
+#pragma unroll
+          for (int b = 0; b < YB; ++b) Tl[b] = seg_entry_lane(tab, dead[b]);
+          zsum_uniform_lane<YB>(zt, Tl, c2e, F, kend, k2);
+        } else {
+          zsum_uniform<YB>(zt, uniform(seg_entry(tab, kTabTClamp)), c2e, F, kend, k2);
+        }
+      } else {
+        const int k2 = seg_first_batch(
+            [&](double g) {
+              bool c = true;
+#pragma unroll
+              for (int b = 0; b < YB; ++b) c = c && seg_clamped(c2e[b], g, Mv);
+              return __all(c) != 0;
+            },
+            [&](int k) { return zt[k].g4; }, kend, kKUnroll);
+        if (k2 > 0) zsum<YB, EXPV, true>(zt, tab, c2e, F, k2);
+        zsum_uniform<YB>(zt, uniform(seg_entry(tab, kTabTClamp)), c2e, F, kend, k2);
+      }
+      after_general();
     }
   } else if (EXPV == kExpTable && __all(small)) {
     zsum<YB, EXPV, false>(zt, tab, c2e, F, kend);
@@ -813,6 +976,12 @@ __device__ __forceinline__ double wave_sum(double v) {
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, kWaveSize);
   return v;
 }
+// (LZQ_PASS_LEAN: the same butterfly through shfl_xor_rederived)
+__device__ __forceinline__ double wave_sum_rederived(double v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += shfl_xor_rederived(v, off);
+  return v;
+}
 
 // Lane index 0..63, re-derived where it is used (v_mbcnt; volatile, so it is not kept live).
 __device__ __forceinline__ int lane_id() {
@@ -833,11 +1002,19 @@ __device__ __forceinline__ int lane_id() {
 // post-loop code (one unrolled copy per slot, shared by the group sizes: the code is what a launch
 // fetches from HBM besides its 48 B per point).  Returns the number of passes run and integrated;
 // 0: none qualifies, nothing was touched, and the caller runs the single pass.
-template <int G, int NZ, typename Win, typename Slot>
+//
+// LEAN (LZQ_PASS_LEAN): y and e^y of the slots stay live from the classification to the integration --
+// the accumulate-only loops have the room -- instead of being formed again, and a group whose G slots
+// touch neither end of the y-grid (y_pass_interior on n_lin, lzq_ynode.h) forms y and the weight
+// without the end-of-grid selects.
+template <int G, int NZ, typename Win, bool LEAN, typename Slot>
 __device__ __forceinline__ int yb_group(Slot* slots, int w, const ZNode* __restrict__ zt, int nzp, const double* tab,
-                                        int base, int fit) {
+                                        int base, int fit, int n_lin) {
   const int nz = NZ > 0 ? NZ : nzp;
   double c2g[G];
+  constexpr int K = LEAN ? (G < kLeanKeep ? G : kLeanKeep) : 0;  // the slots whose y and e^y are kept
+  [[maybe_unused]] double yk[K > 0 ? K : 1], ek[K > 0 ? K : 1];
+  [[maybe_unused]] const bool interior = LEAN && y_pass_interior(base, G * kWaveSize, n_lin);
   int cls = 0;
   {
     const int lane = lane_id();
@@ -849,8 +1026,10 @@ __device__ __forceinline__ int yb_group(Slot* slots, int w, const ZNode* __restr
 #pragma unroll
     for (int b = 0; b < G; ++b) {
       // (a slot past `fit` is formed too -- y_node is arithmetic on j -- and never looked at)
-      const double yv = y_node(s, base + b * kWaveSize + lane);
-      const double ey = exp_sc(pymax(pymin(yv, 50.0), -50.0));               // fpy:161
+      const int j = base + b * kWaveSize + lane;
+      const double yv = interior ? y_node_interior(s.y_lo, s.step, j) : y_node(s, j);
+      const double ey = exp_y<LEAN>(yv);                                     // fpy:161
+      if (b < K) yk[b] = yv, ek[b] = ey;
       c2g[b] = ((s.cneg * ey) * kLog2E) * c2_scale<kExpTable>();             // fpy:163, as in yb_wave
       cls |= seg_group_slot(c2g[b], g_0, g_1, g_last, Mv, Av) << (2 * b);
     }
@@ -904,10 +1083,22 @@ __device__ __forceinline__ int yb_group(Slot* slots, int w, const ZNode* __restr
       const int lane2 = lane_id();
       const QuadSetup& sr = slots[wr].s;
       const int j = base + b * kWaveSize + lane2;  // < n: the group's passes are full
-      const double yv = y_node(sr, j);
-      const double ey = exp_sc(pymax(pymin(yv, 50.0), -50.0));
-      const double wt = y_weight(sr, j, yv);
-      const YFactors f = y_factors(slots[wr].s, yv, ey, wt, [&](double yy) { return Win::eval(slots[wr], yy); });
+      double yv, ey, wt;
+      if constexpr (LEAN) {
+        if (b < K) {
+          yv = yk[b], ey = ek[b];
+        } else {
+          yv = interior ? y_node_interior(sr.y_lo, sr.step, j) : y_node(sr, j);
+          ey = exp_y<true>(yv);
+        }
+        wt = interior ? y_weight_interior(sr.y_lo, sr.step, j, yv) : y_weight(sr, j, yv);
+      } else {
+        yv = y_node(sr, j);
+        ey = exp_sc(pymax(pymin(yv, 50.0), -50.0));
+        wt = y_weight(sr, j, yv);
+      }
+      const YFactors f =
+          y_factors(slots[wr].s, yv, ey, wt, [&](double yy) { return win_eval<LEAN, Win>(slots[wr], yy); });
       slots[wr].acc[lane2] = __builtin_fma(f.w, integrand_from(f, Fb), slots[wr].acc[lane2]);
     }
   }
@@ -921,7 +1112,9 @@ __device__ __forceinline__ int yb_group(Slot* slots, int w, const ZNode* __restr
 //   * the point's QuadSetup lives in the wave's LDS slot (~44 SGPRs otherwise); each pass
 //     re-reads the fields it needs with broadcast ds_reads, through a slot index made opaque
 //     per pass so that the reads are not hoisted back out of the y-loop;
-//   * y, e^y and the weight are re-formed after the z-loop (same operations, same bits);
+//   * y, e^y and the weight are re-formed after the z-loop (same operations, same bits) -- after
+//     the table-lookup loop zsum<> only, in the dense mode (LZQ_PASS_LEAN): the other z-loops have
+//     room for them, and a pass that ran zsum<> re-forms them on its own branch of zsum_dispatch;
 //   * the lane's running sum over its y-nodes sits in the slot (LZQ_ACC_LDS).
 // Without this the kernel spilled ~200 B/lane to scratch around every z-loop.
 // MODE (see lzq_sweep_grid_reuse): kYbDense computes every F(y_j) = sum_k omega_k 2^(c2_j g_k)
@@ -953,6 +1146,10 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
   // a window of the point's own (lzq_window.hip) groups two passes at most: with four, the F of the
   // passes still to be integrated and the window's evaluation do not fit the 64 VGPRs (4 spilled)
   constexpr int kGroupMax = __is_same(Win, SlotGaussWindow) ? kGroupSeg : (kGroupSeg < 2 ? kGroupSeg : 2);
+  // the lean per-pass work (LZQ_PASS_LEAN): where the grouping is, and for its reason
+  constexpr bool kLeanHere = kLeanPass && kGroupHere;
+  // n where the grid is (double)j * step + y_lo, 0 where numpy's step == 0 branch is taken: an SGPR
+  [[maybe_unused]] const int n_lin = kLeanHere ? __builtin_amdgcn_readfirstlane(y_lin_count(slots[w].s.step, n)) : 0;
   [[maybe_unused]] bool grp = true;
   for (int base = 0; base < n; base += per_pass) {
     if constexpr (kGroupHere) {
@@ -960,7 +1157,7 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
       if (grp && !truncate) {
         int ran = 0;
         const int fit = (n - base) / kWaveSize;  // the full passes left
-        if (fit >= 2) ran = yb_group<kGroupMax, NZ, Win>(slots, w, zt, nzp, tab, base, fit);
+        if (fit >= 2) ran = yb_group<kGroupMax, NZ, Win, kLeanHere>(slots, w, zt, nzp, tab, base, fit, n_lin);
         if (ran) {
           base += (ran - 1) * per_pass;
           continue;
@@ -988,19 +1185,38 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
       asm volatile("" : "+s"(wo));
       const QuadSetup& s = slots[wo].s;
       double c2[YB];
+      [[maybe_unused]] const bool interior = kLeanHere && y_pass_interior(base, per_pass, n_lin);
 #pragma unroll
       for (int b = 0; b < YB; ++b) {
         const int j = base + b * kWaveSize + lane;
-        const int jj = j < n ? j : n - 1;  // tail lanes recompute the last node with weight 0
-        yv[b] = y_node(s, jj);
-        ey[b] = exp_sc(pymax(pymin(yv[b], 50.0), -50.0));                          // fpy:161
-        c2[b] = ((s.cneg * ey[b]) * kLog2E) * c2_scale<EXPV>();                 // fpy:163 c, log2 units
-        wt[b] = j < n ? y_weight(s, jj, yv[b]) : 0.0;
+        if constexpr (kLeanHere) {
+          y_triple<true>(s, j, n, interior, yv[b], ey[b], wt[b]);
+          c2[b] = ((s.cneg * ey[b]) * kLog2E) * c2_scale<EXPV>();               // fpy:163 c, log2 units
+        } else {
+          const int jj = j < n ? j : n - 1;  // tail lanes recompute the last node with weight 0
+          yv[b] = y_node(s, jj);
+          ey[b] = exp_sc(pymax(pymin(yv[b], 50.0), -50.0));                        // fpy:161
+          c2[b] = ((s.cneg * ey[b]) * kLog2E) * c2_scale<EXPV>();               // fpy:163 c, log2 units
+          wt[b] = j < n ? y_weight(s, jj, yv[b]) : 0.0;
+        }
 #if LZQ_YFACT_EARLY
         fy[b] = y_factors(s, yv[b], ey[b], wt[b]);
 #endif
       }
-      grp = zsum_dispatch<YB, EXPV, NZ>(zt, nzp, tab, c2, F, truncate);
+      if constexpr (kLeanHere) {
+        // y, e^y and the weight stay live through the lean loops; a pass that ran the table-lookup loop
+        // re-forms them on its own branch (zsum_dispatch's after_general), as every pass did before
+        grp = zsum_dispatch<YB, EXPV, NZ>(zt, nzp, tab, c2, F, truncate, [&]() {
+          int wa = w;
+          asm volatile("" : "+s"(wa));
+          const int la = lane_id();
+#pragma unroll
+          for (int b = 0; b < YB; ++b)
+            y_triple<true, kLeanKeep1>(slots[wa].s, base + b * kWaveSize + la, n, interior, yv[b], ey[b], wt[b]);
+        });
+      } else {
+        grp = zsum_dispatch<YB, EXPV, NZ>(zt, nzp, tab, c2, F, truncate);
+      }
       if constexpr (MODE == kYbTable) {
 #pragma unroll
         for (int b = 0; b < YB; ++b) {
@@ -1013,7 +1229,13 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
     int wr = w;
     asm volatile("" : "+s"(wr));
     const int lane2 = lane_id();
-    if (MODE == kYbReuse || (LZQ_Y_RECOMPUTE && !LZQ_YFACT_EARLY)) {
+    if constexpr (kLeanHere && kLeanKeep1 != 7) {
+      const bool interior = y_pass_interior(base, per_pass, n_lin);
+#pragma unroll
+      for (int b = 0; b < YB; ++b)
+        y_triple<true, 7 & ~kLeanKeep1>(slots[wr].s, base + b * kWaveSize + lane2, n, interior, yv[b], ey[b], wt[b]);
+    }
+    if (!kLeanHere && (MODE == kYbReuse || (LZQ_Y_RECOMPUTE && !LZQ_YFACT_EARLY))) {
       const QuadSetup& sr = slots[wr].s;
 #pragma unroll
       for (int b = 0; b < YB; ++b) {
@@ -1031,7 +1253,7 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
     for (int b = 0; b < YB; ++b) {
 #if !LZQ_YFACT_EARLY
       const YFactors f =
-          y_factors(slots[wr].s, yv[b], ey[b], wt[b], [&](double yy) { return Win::eval(slots[wr], yy); });
+          y_factors(slots[wr].s, yv[b], ey[b], wt[b], [&](double yy) { return win_eval<kLeanHere, Win>(slots[wr], yy); });
 #else
       const YFactors& f = fy[b];
 #endif
@@ -1042,7 +1264,8 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
 #endif
   }
 #if LZQ_ACC_LDS
-  return wave_sum(slots[w].acc[lane_id()]);
+  if constexpr (kLeanHere) return wave_sum_rederived(slots[w].acc[lane_id()]);
+  else return wave_sum(slots[w].acc[lane_id()]);
 #else
   return wave_sum(acc);
 #endif

@@ -29,6 +29,14 @@ seg_group_slot / seg_group_kind): how many of the point's passes run in groups o
 and dead, their share of the (pass, node) pairs, and the classifications that come to nothing.  The
 instruction counts do not change; what the groups buy is issue time (profiles/round11).
 
+Last, the lean passes (LZQ_PASS_LEAN).  The one pass that mixes dead and clamped lanes is planned by
+tests/zsum_mixed_host.cpp (seg_clamped_or_dead): its k2 and the nodes from there on, which run the
+six-operation node with the entry held per lane instead of the nine-operation clamped general node
+(the max, the address and the insert fewer; the LDS read too).  The once-per-pass work is counted in the
+ISA by tools/pass_valu.py (profiles/round12/pass_valu.json: both builds, per path, weighted by this
+plan); together they predict the VALU per wave-node from the PMC of the build without them
+(profiles/round12/parent_pmc_summary.json).
+
     python tools/uniform_segment_share.py
 """
 import json
@@ -42,6 +50,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import test_zsum_dead_segment_host as H  # noqa: E402
 import test_zsum_frozen_host as HF        # noqa: E402
 import test_zsum_group_host as HG         # noqa: E402
+import test_zsum_mixed_host as HM         # noqa: E402
 import zsum_ref as Z                      # noqa: E402
 
 
@@ -94,6 +103,44 @@ def group_counts(g, c2_nodes, gmax=4):
         "classifications_refused": int(((size == 1) & (tried == 1)).sum())}}
 
 
+def lean_counts(g, c2):
+    """The mixed pass of LZQ_PASS_LEAN on the passes of c2 and, with the per-pass count of
+    profiles/round12/pass_valu.json, what both predict from the parent's PMC."""
+    import ctypes
+    import subprocess
+    import tempfile
+    so = os.path.join(tempfile.mkdtemp(), "zsum_mixed_host.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I",
+                    os.path.join(ROOT, HM.PKG_NAME, "csrc"), os.path.join(ROOT, "tests", "zsum_mixed_host.cpp"), "-o", so],
+                   check=True)
+    L = ctypes.CDLL(so)
+    L.zmixed_passes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, HM.DP, HM.DP, ctypes.c_int, HM.DP,
+                                ctypes.c_long, HM.DP, HM.DP, HM.UP, HM.IP]
+    plan = HM.run(L, g, c2, HM.NEW, 0)[3]
+    mixed = plan[:, 0] == HM.MIXED
+    nodes = int(plan[:, 2].sum())
+    n_mixed = int((plan[:, 2] - plan[:, 1])[mixed].sum())
+    p12 = _parent("round12")
+    out = {"passes_mixed": np.flatnonzero(mixed).tolist(), "mixed_dead_lanes": plan[mixed, 3].tolist(),
+           "mixed_k2": plan[mixed, 1].tolist(), "nodes_mixed_suffix": n_mixed, "mixed_suffix_share": n_mixed / nodes,
+           "mixed_saved_valu_per_wave_node": 3.0 * n_mixed / nodes}
+    pv = os.path.join(ROOT, "profiles", "round12", "pass_valu.json")
+    if os.path.exists(pv):
+        with open(pv) as f:
+            rec = json.load(f)
+        out.update({"per_pass_valu_parent": rec["parent"]["c2_weighted_valu_per_pass"],
+                    "per_pass_valu_new": rec["new"]["c2_weighted_valu_per_pass"],
+                    "per_pass_saved_valu_per_wave_node": rec["saved_valu_per_wave_node"],
+                    "predicted_valu_per_wave_node": p12["valu_insts_per_wave_node"] - rec["saved_valu_per_wave_node"]
+                    - 3.0 * n_mixed / nodes,
+                    "predicted_valu_per_wave_node_per_pass_only": p12["valu_insts_per_wave_node"]
+                    - rec["saved_valu_per_wave_node"],
+                    "predicted_valu_per_wave_node_mixed_only": p12["valu_insts_per_wave_node"] - 3.0 * n_mixed / nodes,
+                    "predicted_int32_per_wave_node": p12["valu_mix_per_wave_node"]["int32"] - 2.0 * n_mixed / nodes,
+                    "predicted_lds_per_wave_node": p12["lds_insts_per_wave_node"] - n_mixed / nodes})
+    return {"pass_lean": out}
+
+
 def main():
     B, Tp, I_p = 100.0, 100.0, 0.34                  # yields_config_equal_mass.json (C2's base)
     y_of = lambda T: 0.5 * B * ((Tp / T) ** 2 - 1.0)
@@ -125,7 +172,7 @@ def main():
     mix9 = dict(p9["valu_mix_per_wave_node"])
     mix9["fma_f64"] -= 2.0 * dead / nodes
     mix9["mul_f64"] -= dead / nodes
-    print(json.dumps({**grouped, **frozen_counts(g, c2),
+    print(json.dumps({**grouped, **frozen_counts(g, c2), **lean_counts(g, c2),
         "passes": int(len(path)), "nodes_per_point": nodes,
         "passes_whole_uniform": int(((path == H.ZERO) | (path == H.DEAD)).sum()),
         "passes_clamp_free": int((path == H.FREE).sum()),
