@@ -40,25 +40,6 @@ namespace lzq {
 // ---------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------
-// Block-level table staging of the dense kernels: the exp table into LDS, and with LZQ_ZLDS
-// (an ablation build) the default grid's z nodes too; runtime grids (NZ = 0) keep theirs global.
-#if LZQ_ZLDS
-#define LZQ_STAGE_TABLES(NZ)                                   \
-  __shared__ LdsTables lds;                                    \
-  const double* tab;                                           \
-  if constexpr (NZ == kNZ) {                                   \
-    stage_tables<EXPV>(zt, &lds);                              \
-    tab = lds.t;                                               \
-    zt = lds.z;                                                \
-  } else {                                                     \
-    tab = stage_table<EXPV>(gtab, lds.t);                      \
-  }
-#else
-#define LZQ_STAGE_TABLES(NZ)          \
-  __shared__ double lds_tab[kTabN]; \
-  const double* tab = stage_table<EXPV>(gtab, lds_tab);
-#endif
-
 // NZ: kNZ for the reference's default z grid (the headline build, node count a compile-time
 // constant), 0 for a runtime grid of nzp (padded) nodes -- see zsum_dispatch.
 template <int YB, int EXPV, int NZ>
@@ -69,7 +50,8 @@ __global__ __launch_bounds__(kBlock, LZQ_MIN_WAVES) void yields_points_kernel(co
                                                               const ZNode* __restrict__ zt, int32_t nzp,
                                                               const double* __restrict__ gtab,
                                                               lzq_yield* __restrict__ out, int truncate) {
-  LZQ_STAGE_TABLES(NZ)
+  __shared__ double lds_tab[kTabN];
+  const double* tab = stage_table<EXPV>(gtab, lds_tab);
   __shared__ WaveSlot slots[kWavesPerBlock];
   const int lane = threadIdx.x & (kWaveSize - 1);
   // wave index and point index formed from readfirstlane, so they live in SGPRs (a VGPR copy
@@ -94,7 +76,8 @@ __global__ __launch_bounds__(kBlock, LZQ_MIN_WAVES) void yields_grid_kernel(lzq_
                                                             const ZNode* __restrict__ zt, int32_t nzp,
                                                             const double* __restrict__ gtab,
                                                             lzq_yield* __restrict__ out, int truncate) {
-  LZQ_STAGE_TABLES(NZ)
+  __shared__ double lds_tab[kTabN];
+  const double* tab = stage_table<EXPV>(gtab, lds_tab);
   __shared__ WaveSlot slots[kWavesPerBlock];
   const int lane = threadIdx.x & (kWaveSize - 1);
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // SGPR (see yields_points_kernel)

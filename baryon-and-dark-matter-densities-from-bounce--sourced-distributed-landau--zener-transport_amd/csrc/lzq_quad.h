@@ -21,6 +21,45 @@
 
 namespace lzq {
 
+// The five fast-path levels of the dense z-sum and y-loop.  Each is a switch only because a host test
+// builds it with =0 and pins the result to the recorded machine code of the commit before it; the full
+// account of every level is DESIGN.md §4.1.  A level whose "needs" are not at their defaults is off.
+//
+//   switch            values   what the level adds                                        needs
+//   LZQ_ZERO_SEG      0, 1     zero passes (round(u) = 0 in every lane) skip the range    --
+//                              reduction: four FP64 operations per node, not six
+//   LZQ_DEAD_SEG      0, 1     all-dead zero passes form the node value once: the node    ZERO_SEG
+//                              is F's accumulate alone (zsum_dead)
+//   LZQ_FROZEN_SEG    0, 1, 2  1: a zero pass's tail with s frozen is the accumulate      ZERO_SEG, DEAD_SEG
+//                              alone (zsum_held); 2: also a clamp-free pass's tail with
+//                              t frozen runs without the lookup (zsum_frozen_t)
+//   LZQ_GROUP_SEG     0, 2, 4  up to that many consecutive accumulate-only passes are     FROZEN_SEG >= 1
+//                              swept through z together (yb_group)
+//   LZQ_PASS_LEAN     0, 1     y, e^y and the weight stay live across the loops that      all four at their
+//                              have room; clamp-free exp_sc; interior y-nodes; the        defaults
+//                              dead/clamped mixed pass (zsum_uniform_lane)
+#ifndef LZQ_ZERO_SEG
+#define LZQ_ZERO_SEG 1
+#endif
+#ifndef LZQ_DEAD_SEG
+#define LZQ_DEAD_SEG 1
+#endif
+#ifndef LZQ_FROZEN_SEG
+#define LZQ_FROZEN_SEG 2
+#endif
+#ifndef LZQ_GROUP_SEG
+#define LZQ_GROUP_SEG 4
+#endif
+#ifndef LZQ_PASS_LEAN
+#define LZQ_PASS_LEAN 1
+#endif
+static_assert(LZQ_GROUP_SEG == 0 || LZQ_GROUP_SEG == 2 || LZQ_GROUP_SEG == 4, "LZQ_GROUP_SEG is 0, 2 or 4");
+static_assert(LZQ_PASS_LEAN == 0 || LZQ_PASS_LEAN == 1, "LZQ_PASS_LEAN is 0 or 1");
+constexpr int kFrozenSeg = (LZQ_ZERO_SEG != 0 && LZQ_DEAD_SEG != 0) ? LZQ_FROZEN_SEG : 0;
+constexpr int kGroupSeg = kFrozenSeg >= 1 ? LZQ_GROUP_SEG : 0;
+constexpr bool kLean = LZQ_ZERO_SEG == 1 && LZQ_DEAD_SEG == 1 && LZQ_FROZEN_SEG == 2 && LZQ_GROUP_SEG == 4 &&
+                       LZQ_PASS_LEAN == 1;
+
 constexpr int kNZ = LZQ_NZ;
 constexpr int kWaveSize = 64;
 // The block is sized so that the LDS copies of the exp table that fit in a CU's 160 KB carry
@@ -42,103 +81,6 @@ constexpr int kWavesPerBlock = kBlock / kWaveSize;
 #ifndef LZQ_MIN_WAVES
 #define LZQ_MIN_WAVES 8
 #endif
-// z-table source: 0 = wave-uniform scalar loads (SGPR operands), 1 = staged in LDS and read
-// with broadcast ds_read_b128 (keeps every LGKM operation of the loop in order, so the
-// compiler can use counted lgkmcnt waits instead of draining behind SMEM)
-#ifndef LZQ_ZLDS
-#define LZQ_ZLDS 0
-#endif
-#ifndef LZQ_YFACT_EARLY
-#define LZQ_YFACT_EARLY 0
-#endif
-// re-form y / e^y / weight after the z-loop instead of keeping them live across it
-#ifndef LZQ_Y_RECOMPUTE
-#define LZQ_Y_RECOMPUTE 1
-#endif
-// keep yb_wave's per-lane running sum in the wave's LDS slot instead of a VGPR pair
-#ifndef LZQ_ACC_LDS
-#define LZQ_ACC_LDS 1
-#endif
-#ifndef LZQ_SPLIT_CLAMP
-#define LZQ_SPLIT_CLAMP 0  // clamped passes: the z-nodes no lane can clamp run clamp-free (zsum_dispatch)
-#endif
-// stretches of a pass on which every lane reads ONE table entry at every node (all of a pass whose
-// lanes all have round(u) = 0 or are dead; the all-lanes-clamped tail of a clamped pass) fetch it
-// once and run the node without its lookup (zsum_uniform, zsum_dispatch); 0: every node looks up
-#ifndef LZQ_UNIFORM_SEG
-#define LZQ_UNIFORM_SEG 1
-#endif
-// the whole-pass zero stretch (every lane has round(u) = 0 at every node) also runs without the
-// range reduction, whose results the pass test has already fixed: t = M, w = A (seg_node_zero in
-// lzq_exp2.h; four FP64 operations per node instead of six); 0: the six-operation uniform node
-#ifndef LZQ_ZERO_SEG
-#define LZQ_ZERO_SEG 1
-#endif
-// a whole-pass zero stretch whose 64 lanes are all dead (c2e = +0.0 in every lane) also forms the
-// node's value once per pass: s = fma(+0 * g, A) = A, so q and v are one number at every node and
-// only F's accumulate runs per node (seg_node_dead in lzq_exp2.h, zsum_dead; one FP64 operation per
-// node instead of four).  Needs LZQ_ZERO_SEG; 0: those passes run the four-operation zero node
-#ifndef LZQ_DEAD_SEG
-#define LZQ_DEAD_SEG 1
-#endif
-// the tail of a pass from the batch at which every lane's rounded intermediate has reached the value
-// it has at the last executed node (gamma4 saturates; seg_frozen_s / seg_frozen_t in lzq_exp2.h):
-//   1: zero passes -- s is frozen, so v is a per-lane constant and the node is F's accumulate alone
-//      (zsum_held; one FP64 operation per node instead of four);
-//   2: also clamp-free passes -- t is frozen, so the entry and w are per-lane constants and the node
-//      is s, q, v and F's fma (zsum_frozen_t; four FP64 operations instead of six, no lookup);
-//   0: off.  Needs LZQ_UNIFORM_SEG, LZQ_ZERO_SEG and LZQ_DEAD_SEG (without one of them it is off)
-#ifndef LZQ_FROZEN_SEG
-#define LZQ_FROZEN_SEG 2
-#endif
-constexpr int kFrozenSeg = (LZQ_UNIFORM_SEG != 0 && LZQ_ZERO_SEG != 0 && LZQ_DEAD_SEG != 0) ? LZQ_FROZEN_SEG : 0;
-// runs of consecutive passes that are F's accumulate alone from node 0 (all 64 lanes dead, or every
-// lane's s frozen at A from the first node) are swept through z together, up to LZQ_GROUP_SEG (2 or 4)
-// passes at a time: each lane then carries that many independent F chains and every omega' feeds that
-// many fma (yb_group; the dense yb_wave only).  Each chain runs in node order from 0 and the passes are
-// integrated in pass order, so the bits are the single pass's and no node is skipped.  0: off.
-// Needs LZQ_FROZEN_SEG >= 1 and the default y-loop (LZQ_ACC_LDS, LZQ_Y_RECOMPUTE, no LZQ_YFACT_EARLY)
-#ifndef LZQ_GROUP_SEG
-#define LZQ_GROUP_SEG 4
-#endif
-static_assert(LZQ_GROUP_SEG == 0 || LZQ_GROUP_SEG == 2 || LZQ_GROUP_SEG == 4, "LZQ_GROUP_SEG is 0, 2 or 4");
-constexpr int kGroupSeg =
-    (kFrozenSeg >= 1 && LZQ_ACC_LDS != 0 && LZQ_Y_RECOMPUTE != 0 && LZQ_YFACT_EARLY == 0) ? LZQ_GROUP_SEG : 0;
-// the once-per-pass work of the dense y-loop without what the result does not need (yb_wave, yb_group,
-// zsum_dispatch):
-//   * y, e^y and the trapezoid weight stay live from the pre-loop code to the integration on every pass
-//     that does not enter the table-lookup loop zsum<> (which needs ~60 of the 64 VGPRs); a pass that
-//     does re-forms them on its own branch, as every pass did before;
-//   * e^y takes its [-50, 50] clamp as one max and one min (y is a finite linspace element) and an
-//     exp_sc without the range clamp that cannot fire behind it; the Gaussian window, whose argument
-//     is <= 0, keeps the lower clamp only;
-//   * a pass that touches neither end of the y-grid forms y and the weight without the end-of-grid
-//     selects (lzq_ynode.h);
-//   * a clamped pass that holds dead lanes runs its suffix from the batch at which every LIVE lane is
-//     clamped through the six-operation uniform node with the entry held per lane (zsum_uniform_lane).
-// Same operations on the same operands at every node, no node skipped.  0: the code before it.  Needs
-// the default segment paths (LZQ_UNIFORM_SEG, LZQ_ZERO_SEG, LZQ_DEAD_SEG, LZQ_FROZEN_SEG, LZQ_GROUP_SEG)
-// and the default y-loop; the table and reuse modes keep the old pre- and post-loop code.
-// A/B builds: 2 the per-pass work only, 3 the mixed pass only.
-#ifndef LZQ_PASS_LEAN
-#define LZQ_PASS_LEAN 1
-#endif
-static_assert(LZQ_PASS_LEAN >= 0 && LZQ_PASS_LEAN <= 3, "LZQ_PASS_LEAN is 0, 1, 2 or 3");
-constexpr bool kLeanDefaults = LZQ_UNIFORM_SEG == 1 && LZQ_ZERO_SEG == 1 && LZQ_DEAD_SEG == 1 && LZQ_FROZEN_SEG == 2 &&
-                               LZQ_GROUP_SEG == 4 && LZQ_ACC_LDS != 0 && LZQ_Y_RECOMPUTE != 0 && LZQ_YFACT_EARLY == 0;
-constexpr bool kLeanPass = kLeanDefaults && (LZQ_PASS_LEAN == 1 || LZQ_PASS_LEAN == 2);
-// the slots of a group whose y and e^y stay live across its sweep (4, 2 or 0: the others re-form them)
-#ifndef LZQ_PASS_LEAN_KEEP
-#define LZQ_PASS_LEAN_KEEP 4
-#endif
-constexpr int kLeanKeep = LZQ_PASS_LEAN_KEEP;
-// which of y (1), e^y (2) and the weight (4) a single pass keeps live across its lean loops; the others
-// are re-formed after the z-loop on every pass
-#ifndef LZQ_PASS_LEAN_KEEP1
-#define LZQ_PASS_LEAN_KEEP1 7
-#endif
-constexpr int kLeanKeep1 = LZQ_PASS_LEAN_KEEP1;
-constexpr bool kLeanMixed = kLeanDefaults && (LZQ_PASS_LEAN == 1 || LZQ_PASS_LEAN == 3);
 constexpr int kKUnroll = LZQ_KUNROLL;  // z-nodes per scalar-load batch (must divide 1200)
 constexpr int kYB = LZQ_YB;            // y-nodes per lane per pass (independent chains)
 static_assert(kNZ % kKUnroll == 0, "z unroll must divide nz");
@@ -234,10 +176,6 @@ __device__ __forceinline__ double vgpr_const(double x) {
 // constants are read from constant memory through an offset made opaque per call, so they
 // come in by scalar loads where needed: the libm exp's coefficients were hoisted out of the
 // y-loop into VGPRs and spilled to scratch across the z-loop (which needs ~60 of 64 VGPRs).
-#ifndef LZQ_YFAST
-#define LZQ_YFAST 7  // bit mask (A/B builds): 1 SGPR Horner steps, 2 rsqrt, 4 1/sigma product
-#endif
-
 LZQ_QUAD_CONST_LINKAGE __constant__ double kExpC[15] = {
     0x1.6124613a86d09p-33, 0x1.1eed8eff8d898p-29, 0x1.ae64567f544e4p-26, 0x1.27e4fb7789f5cp-22,
     0x1.71de3a556c734p-19, 0x1.a01a01a01a01ap-16, 0x1.a01a01a01a01ap-13, 0x1.6c16c16c16c17p-10,
@@ -260,7 +198,7 @@ __device__ __forceinline__ double exp_sc(double x) {
   r = __builtin_fma(-k, c[14], r);
   double p = c[0];
 #pragma unroll
-  for (int i = 1; i < 12; ++i) p = (LZQ_YFAST & 1) ? fma_vvs(p, r, c[i]) : __builtin_fma(p, r, c[i]);
+  for (int i = 1; i < 12; ++i) p = fma_vvs(p, r, c[i]);  // the coefficient as the fma's SGPR operand
   p = __builtin_fma(p, r, 1.0);  // (e^r - 1) / r
   p = __builtin_fma(p, r, 1.0);  // e^r
   return __builtin_ldexp(p, (int)k);
@@ -319,22 +257,13 @@ __device__ __forceinline__ double rsqrt_pos(double d) {
 template <typename WinF>
 __device__ __forceinline__ YFactors y_factors(const QuadSetup& s, double y, double expy, double wt, const WinF& wf) {
   YFactors f;
-  double T, dTdy, H;
-  if (LZQ_YFAST & 2) {
-    // 2y/B stays a correctly rounded division: near y = -B/2 (T_max/T_p large) 1 + 2y/B cancels,
-    // and the product with a rounded 2/B moved Y_B by 6.7e-13 on a golden point (diag_golden.py)
-    const double denom = pymax(1.0 + 2.0 * y / s.Bc, 1e-12);  // fpy:252-253
-    const double rs = rsqrt_pos(denom);
-    T = s.Tp * rs;                                           // fpy:254
-    dTdy = s.dT0 * ((rs * rs) * rs);                         // fpy:255  denom**(-1.5)
-    H = s.H0 * T * T * (1.0 / kMplGeV);                      // fpy:258 via fpy:85
-  } else {
-    const double denom = pymax(1.0 + 2.0 * y / s.Bc, 1e-12);
-    const double sd = sqrt(denom);
-    T = s.Tp / sd;
-    dTdy = s.dT0 * (1.0 / (denom * sd));
-    H = s.H0 * T * T / kMplGeV;
-  }
+  // 2y/B stays a correctly rounded division: near y = -B/2 (T_max/T_p large) 1 + 2y/B cancels,
+  // and the product with a rounded 2/B moved Y_B by 6.7e-13 on a golden point (diag_golden.py)
+  const double denom = pymax(1.0 + 2.0 * y / s.Bc, 1e-12);  // fpy:252-253
+  const double rs = rsqrt_pos(denom);
+  const double T = s.Tp * rs;                               // fpy:254
+  const double dTdy = s.dT0 * ((rs * rs) * rs);             // fpy:255  denom**(-1.5)
+  const double H = s.H0 * T * T * (1.0 / kMplGeV);          // fpy:258 via fpy:85
   double T3 = (T * T) * T;
   double sE = s.s0 * T3;                                  // fpy:259 via fpy:88
   double n_eq, vbar;                                      // fpy:90-120, strict T > m/3 branch
@@ -360,7 +289,7 @@ __device__ __forceinline__ YFactors y_factors(const QuadSetup& s, double y, doub
 // (LEAN, LZQ_PASS_LEAN: the argument is <= 0 or NaN, so exp_sc's upper clamp cannot fire and is left out)
 template <bool LEAN = false>
 __device__ __forceinline__ double gauss_window(const QuadSetup& s, double y) {
-  double q = (LZQ_YFAST & 4) ? y * s.isig : y / s.sig;
+  const double q = y * s.isig;
   return exp_sc<LEAN ? kExpLow : kExpBoth>(-0.5 * (q * q));
 }
 
@@ -396,23 +325,18 @@ __device__ __forceinline__ double y_weight(const QuadSetup& s, int j, double y) 
 // (wave-uniform; LZQ_PASS_LEAN only): the pass touches neither end of the y-grid (y_pass_interior,
 // lzq_ynode.h) and takes the forms without the end-of-grid selects; otherwise j may lie past the grid
 // (a tail lane of the last pass), which recomputes the last node with weight 0.
-// WHICH: the values written (kKeepY | kKeepEy | kKeepWt); the others are left as they are.
-constexpr int kKeepY = 1, kKeepEy = 2, kKeepWt = 4;
-template <bool LEAN, int WHICH = 7>
+template <bool LEAN>
 __device__ __forceinline__ void y_triple(const QuadSetup& s, int j, int n, bool interior, double& y, double& ey,
                                          double& wt) {
-  double yj;
   if (LEAN && interior) {
-    yj = y_node_interior(s.y_lo, s.step, j);
-    if constexpr ((WHICH & kKeepWt) != 0) wt = y_weight_interior(s.y_lo, s.step, j, yj);
+    y = y_node_interior(s.y_lo, s.step, j);
+    wt = y_weight_interior(s.y_lo, s.step, j, y);
   } else {
     const int jj = j < n ? j : n - 1;
-    yj = y_node(s, jj);
-    if constexpr ((WHICH & kKeepWt) != 0) wt = j < n ? y_weight(s, jj, yj) : 0.0;
+    y = y_node(s, jj);
+    wt = j < n ? y_weight(s, jj, y) : 0.0;
   }
-  if constexpr ((WHICH & kKeepY) != 0) y = yj;
-  // (one copy behind the branch: the code is what a launch fetches from HBM)
-  if constexpr ((WHICH & kKeepEy) != 0) ey = exp_y<LEAN>(yj);
+  ey = exp_y<LEAN>(y);  // (one copy behind the branch: the code is what a launch fetches from HBM)
 }
 
 // exp variants of the inner loop (lzq_tune(LZQ_TUNE_EXP, ...))
@@ -461,7 +385,7 @@ __device__ __forceinline__ double c2_scale() { return EXPV == kExpTable ? (doubl
 // the lookup (address, ds_read, insert, and the max) returns what it returned at the node before.
 // zsum_dispatch finds those stretches per pass with the loop's own t and runs them through
 // zsum_uniform below: the same six FP64 operations per node on the same operands, the entry fetched
-// once (LZQ_UNIFORM_SEG; 80.3% of the C2 workload's nodes, tools/uniform_segment_share.py).  On the
+// once (80.3% of the C2 workload's nodes, tools/uniform_segment_share.py).  On the
 // first kind of stretch (t = M at every node, 64.0% of the nodes) two of the six are known before
 // the loop starts -- t = M, and w = (M + A) - M = A exactly -- and the node runs the other four:
 // s = fma(c2, g, A), q, v and F's fma, on the operands the six-operation node hands them
@@ -481,12 +405,9 @@ __device__ __forceinline__ double c2_scale() { return EXPV == kExpTable ? (doubl
 // (LZQ_GROUP_SEG, yb_group below; tests/test_zsum_group_host.py, tests/test_gpu_zsum_group.py).
 template <int YB, int EXPV, bool CLAMP = true>
 __device__ __forceinline__ void zsum(const ZNode* __restrict__ zt, const double* tab, const double (&c2)[YB],
-                                     double (&F)[YB], int kend, int kbeg = 0) {
-  // kbeg > 0: nodes kbeg.. continue F's running sums (LZQ_SPLIT_CLAMP), else F starts at 0
-  if (kbeg == 0) {
+                                     double (&F)[YB], int kend) {
 #pragma unroll
-    for (int b = 0; b < YB; ++b) F[b] = 0.0;
-  }
+  for (int b = 0; b < YB; ++b) F[b] = 0.0;
   if constexpr (EXPV == kExpTable) {
     constexpr double kMagic = 0x1.8p52;
     constexpr double kTClamp = kMagic + (double)kTabKMin;  // exact
@@ -498,7 +419,7 @@ __device__ __forceinline__ void zsum(const ZNode* __restrict__ zt, const double*
     for (int i = 0; i < kPolyDeg; ++i) Bv[i] = TabPoly<kTabBits, kPolyDeg>::B[i];
     if constexpr (!kSqForm) Bv[0] = vgpr_const(Bv[0]);
     const char* tabb = reinterpret_cast<const char*>(tab);
-    for (int k = kbeg; k < kend; k += kKUnroll) {
+    for (int k = 0; k < kend; k += kKUnroll) {
       double g4[kKUnroll], om[kKUnroll];
 #pragma unroll
       for (int kk = 0; kk < kKUnroll; ++kk) {
@@ -553,7 +474,7 @@ __device__ __forceinline__ void zsum(const ZNode* __restrict__ zt, const double*
   }
 }
 
-// The uniform-entry loop (LZQ_UNIFORM_SEG): nodes kbeg .. kend of a pass on which every lane's
+// The uniform-entry loop: nodes kbeg .. kend of a pass on which every lane's
 // clamped magic sum tc is one constant at every node, so all 64 lanes would fetch the same entry
 // with the same exponent, node after node.  Ts is that entry as the general loop forms it
 // (seg_entry), wave-uniform, an SGPR pair; a node is then exactly the general node's six FP64
@@ -783,7 +704,7 @@ __device__ __forceinline__ bool zsum_dispatch(const ZNode* __restrict__ zt, int 
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
-      if constexpr (kLeanPass) thr = pymax(thr, shfl_xor_rederived(thr, off));
+      if constexpr (kLean) thr = pymax(thr, shfl_xor_rederived(thr, off));
       else thr = pymax(thr, __shfl_xor(thr, off, kWaveSize));
     }
     thr = uniform(thr);
@@ -796,7 +717,7 @@ __device__ __forceinline__ bool zsum_dispatch(const ZNode* __restrict__ zt, int 
     }
     kend = (lo + kKUnroll - 1) / kKUnroll * kKUnroll;
   }
-  if constexpr (EXPV == kExpTable && kSqForm && LZQ_UNIFORM_SEG) {
+  if constexpr (EXPV == kExpTable && kSqForm) {
     // Uniform-entry segments, decided per pass with the loop's own t = fma(c2, g, M) (lzq_exp2.h):
     //   every lane has t = M at g_max (small |c2|, or dead: c2e = 0): t = M at every node (g4 runs
     //     from >= 0 up to g_max, padding nodes repeat g_max), the whole pass reads T''[0] with
@@ -881,7 +802,7 @@ __device__ __forceinline__ bool zsum_dispatch(const ZNode* __restrict__ zt, int 
       // the first batch at which every LIVE lane is clamped (dead does not depend on k: still monotone;
       // without dead lanes it is the test it was), and from there a pass that holds dead lanes runs the
       // uniform node with each lane's own entry, the others with the one entry in SGPRs as before.
-      if constexpr (kLeanMixed) {
+      if constexpr (kLean) {
         bool any_dead = false;
 #pragma unroll
         for (int b = 0; b < YB; ++b) any_dead = any_dead || dead[b];
@@ -919,24 +840,6 @@ __device__ __forceinline__ bool zsum_dispatch(const ZNode* __restrict__ zt, int 
     }
   } else if (EXPV == kExpTable && __all(small)) {
     zsum<YB, EXPV, false>(zt, tab, c2e, F, kend);
-  } else if (EXPV == kExpTable && LZQ_SPLIT_CLAMP) {
-    // LZQ_SPLIT_CLAMP: the nodes before the first one at which some lane's u = c2 g4 drops below
-    // KMIN + 1 (g4 non-decreasing -- build_ztable refuses other grids -- and c2 <= 0, so u only
-    // falls with k) cannot reach the clamp: they run clamp-free (max(t, M + KMIN) = t there, the
-    // same bits), the rest clamped, F summed in the same node order.  A wave-uniform binary search.
-    int lo = 0, hi = kend;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      const double g = zt[mid].g4;
-      bool low = false;
-#pragma unroll
-      for (int b = 0; b < YB; ++b) low = low || c2e[b] * g < (double)kTabKMin + 1.0;
-      if (__any(low)) hi = mid;
-      else lo = mid + 1;
-    }
-    const int ks = lo / kKUnroll * kKUnroll;
-    if (ks > 0) zsum<YB, EXPV, false>(zt, tab, c2e, F, ks);
-    zsum<YB, EXPV, true>(zt, tab, c2e, F, kend, ks);
   } else {
     zsum<YB, EXPV, true>(zt, tab, c2e, F, kend);
   }
@@ -952,22 +855,6 @@ __device__ __forceinline__ const double* stage_table(const double* __restrict__ 
   for (int i = threadIdx.x; i < kTabN; i += blockDim.x) lds[i] = gtab[i];
   __syncthreads();
   return lds;
-}
-
-// LDS image of the per-block tables: z nodes (19.2 KB) followed by the exp table.
-struct LdsTables {
-  ZNode z[kNZ];
-  double t[kTabN];
-};
-
-// Stage both tables (global layout: ZNode[kNZ] then double[kTabN], see ensure_device).
-template <int EXPV>
-__device__ __forceinline__ void stage_tables(const ZNode* __restrict__ gz, LdsTables* lds) {
-  const double* src = reinterpret_cast<const double*>(gz);
-  double* dst = reinterpret_cast<double*>(lds);
-  constexpr int n = 2 * kNZ + (EXPV == kExpTable ? kTabN : 0);
-  for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
-  __syncthreads();
 }
 
 // Fixed-order xor butterfly over the 64 lanes (every lane ends with the same sum).
@@ -1012,8 +899,7 @@ __device__ __forceinline__ int yb_group(Slot* slots, int w, const ZNode* __restr
                                         int base, int fit, int n_lin) {
   const int nz = NZ > 0 ? NZ : nzp;
   double c2g[G];
-  constexpr int K = LEAN ? (G < kLeanKeep ? G : kLeanKeep) : 0;  // the slots whose y and e^y are kept
-  [[maybe_unused]] double yk[K > 0 ? K : 1], ek[K > 0 ? K : 1];
+  [[maybe_unused]] double yk[G], ek[G];  // LEAN: y and e^y of the slots, kept across the sweep
   [[maybe_unused]] const bool interior = LEAN && y_pass_interior(base, G * kWaveSize, n_lin);
   int cls = 0;
   {
@@ -1029,7 +915,7 @@ __device__ __forceinline__ int yb_group(Slot* slots, int w, const ZNode* __restr
       const int j = base + b * kWaveSize + lane;
       const double yv = interior ? y_node_interior(s.y_lo, s.step, j) : y_node(s, j);
       const double ey = exp_y<LEAN>(yv);                                     // fpy:161
-      if (b < K) yk[b] = yv, ek[b] = ey;
+      yk[b] = yv, ek[b] = ey;
       c2g[b] = ((s.cneg * ey) * kLog2E) * c2_scale<kExpTable>();             // fpy:163, as in yb_wave
       cls |= seg_group_slot(c2g[b], g_0, g_1, g_last, Mv, Av) << (2 * b);
     }
@@ -1083,20 +969,9 @@ __device__ __forceinline__ int yb_group(Slot* slots, int w, const ZNode* __restr
       const int lane2 = lane_id();
       const QuadSetup& sr = slots[wr].s;
       const int j = base + b * kWaveSize + lane2;  // < n: the group's passes are full
-      double yv, ey, wt;
-      if constexpr (LEAN) {
-        if (b < K) {
-          yv = yk[b], ey = ek[b];
-        } else {
-          yv = interior ? y_node_interior(sr.y_lo, sr.step, j) : y_node(sr, j);
-          ey = exp_y<true>(yv);
-        }
-        wt = interior ? y_weight_interior(sr.y_lo, sr.step, j, yv) : y_weight(sr, j, yv);
-      } else {
-        yv = y_node(sr, j);
-        ey = exp_sc(pymax(pymin(yv, 50.0), -50.0));
-        wt = y_weight(sr, j, yv);
-      }
+      const double yv = LEAN ? yk[b] : y_node(sr, j);
+      const double ey = LEAN ? ek[b] : exp_y<false>(yv);
+      const double wt = interior ? y_weight_interior(sr.y_lo, sr.step, j, yv) : y_weight(sr, j, yv);
       const YFactors f =
           y_factors(slots[wr].s, yv, ey, wt, [&](double yy) { return win_eval<LEAN, Win>(slots[wr], yy); });
       slots[wr].acc[lane2] = __builtin_fma(f.w, integrand_from(f, Fb), slots[wr].acc[lane2]);
@@ -1115,7 +990,7 @@ __device__ __forceinline__ int yb_group(Slot* slots, int w, const ZNode* __restr
 //   * y, e^y and the weight are re-formed after the z-loop (same operations, same bits) -- after
 //     the table-lookup loop zsum<> only, in the dense mode (LZQ_PASS_LEAN): the other z-loops have
 //     room for them, and a pass that ran zsum<> re-forms them on its own branch of zsum_dispatch;
-//   * the lane's running sum over its y-nodes sits in the slot (LZQ_ACC_LDS).
+//   * the lane's running sum over its y-nodes sits in the slot.
 // Without this the kernel spilled ~200 B/lane to scratch around every z-loop.
 // MODE (see lzq_sweep_grid_reuse): kYbDense computes every F(y_j) = sum_k omega_k 2^(c2_j g_k)
 // itself (the headline); kYbTable computes them the same way and stores them to Fout instead of
@@ -1127,18 +1002,12 @@ enum YbMode { kYbDense = 0, kYbReuse = 1, kYbTable = 2 };
 template <int YB, int EXPV, int MODE = kYbDense, int NZ = 0, typename Win = SlotGaussWindow, typename Slot>
 __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int nzp, const double* tab, int truncate,
                           const double* __restrict__ Fin = nullptr, double* __restrict__ Fout = nullptr) {
-  static_assert(MODE == kYbDense || !LZQ_YFACT_EARLY, "table modes re-form the y-factors after the z-loop");
-  static_assert(!LZQ_YFACT_EARLY || __is_same(Win, SlotGaussWindow), "the early y-factors take the default window");
   if (slots[w].s.empty) return 0.0;
   // y-node counts are int32 (n_y of the C ABI): 32-bit loop bounds save the SGPRs that
   // would otherwise spill around the z-loop
   const int n = (int)__builtin_bit_cast(int64_t, uniform(__builtin_bit_cast(double, slots[w].s.n)));  // SGPR
   const int per_pass = kWaveSize * YB;
-#if LZQ_ACC_LDS
   slots[w].acc[lane_id()] = 0.0;
-#else
-  double acc = 0.0;
-#endif
   // grouped passes (LZQ_GROUP_SEG): the dense mode only -- the table and reuse modes are its controls.
   // grp (wave-uniform): the pass before ran as the accumulate alone from node 0, or this is the first;
   // only then is a group tried, so a point pays for a handful of classifications that fail
@@ -1147,7 +1016,7 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
   // passes still to be integrated and the window's evaluation do not fit the 64 VGPRs (4 spilled)
   constexpr int kGroupMax = __is_same(Win, SlotGaussWindow) ? kGroupSeg : (kGroupSeg < 2 ? kGroupSeg : 2);
   // the lean per-pass work (LZQ_PASS_LEAN): where the grouping is, and for its reason
-  constexpr bool kLeanHere = kLeanPass && kGroupHere;
+  constexpr bool kLeanHere = kLean && kGroupHere;
   // n where the grid is (double)j * step + y_lo, 0 where numpy's step == 0 branch is taken: an SGPR
   [[maybe_unused]] const int n_lin = kLeanHere ? __builtin_amdgcn_readfirstlane(y_lin_count(slots[w].s.step, n)) : 0;
   [[maybe_unused]] bool grp = true;
@@ -1165,12 +1034,8 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
         grp = false;
       }
     }
-    // only y, e^y and the weight stay live across the z-loop (LZQ_YFACT_EARLY=1: the 7
-    // y-factors instead); the y-factors are formed after it
+    // at most y, e^y and the weight stay live across the z-loop; the y-factors are formed after it
     double yv[YB], ey[YB], wt[YB];
-#if LZQ_YFACT_EARLY
-    YFactors fy[YB];
-#endif
     double F[YB];
     if constexpr (MODE == kYbReuse) {
       const int lane = lane_id();
@@ -1189,19 +1054,10 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
 #pragma unroll
       for (int b = 0; b < YB; ++b) {
         const int j = base + b * kWaveSize + lane;
-        if constexpr (kLeanHere) {
-          y_triple<true>(s, j, n, interior, yv[b], ey[b], wt[b]);
-          c2[b] = ((s.cneg * ey[b]) * kLog2E) * c2_scale<EXPV>();               // fpy:163 c, log2 units
-        } else {
-          const int jj = j < n ? j : n - 1;  // tail lanes recompute the last node with weight 0
-          yv[b] = y_node(s, jj);
-          ey[b] = exp_sc(pymax(pymin(yv[b], 50.0), -50.0));                        // fpy:161
-          c2[b] = ((s.cneg * ey[b]) * kLog2E) * c2_scale<EXPV>();               // fpy:163 c, log2 units
-          wt[b] = j < n ? y_weight(s, jj, yv[b]) : 0.0;
-        }
-#if LZQ_YFACT_EARLY
-        fy[b] = y_factors(s, yv[b], ey[b], wt[b]);
-#endif
+        // (the pass that re-forms the triple after the z-loop needs e^y alone here)
+        if constexpr (kLeanHere) y_triple<true>(s, j, n, interior, yv[b], ey[b], wt[b]);
+        else ey[b] = exp_y<false>(y_node(s, j < n ? j : n - 1));                // fpy:161
+        c2[b] = ((s.cneg * ey[b]) * kLog2E) * c2_scale<EXPV>();                 // fpy:163 c, log2 units
       }
       if constexpr (kLeanHere) {
         // y, e^y and the weight stay live through the lean loops; a pass that ran the table-lookup loop
@@ -1212,7 +1068,7 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
           const int la = lane_id();
 #pragma unroll
           for (int b = 0; b < YB; ++b)
-            y_triple<true, kLeanKeep1>(slots[wa].s, base + b * kWaveSize + la, n, interior, yv[b], ey[b], wt[b]);
+            y_triple<true>(slots[wa].s, base + b * kWaveSize + la, n, interior, yv[b], ey[b], wt[b]);
         });
       } else {
         grp = zsum_dispatch<YB, EXPV, NZ>(zt, nzp, tab, c2, F, truncate);
@@ -1229,46 +1085,29 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
     int wr = w;
     asm volatile("" : "+s"(wr));
     const int lane2 = lane_id();
-    if constexpr (kLeanHere && kLeanKeep1 != 7) {
-      const bool interior = y_pass_interior(base, per_pass, n_lin);
-#pragma unroll
-      for (int b = 0; b < YB; ++b)
-        y_triple<true, 7 & ~kLeanKeep1>(slots[wr].s, base + b * kWaveSize + lane2, n, interior, yv[b], ey[b], wt[b]);
-    }
-    if (!kLeanHere && (MODE == kYbReuse || (LZQ_Y_RECOMPUTE && !LZQ_YFACT_EARLY))) {
+    if constexpr (!kLeanHere) {
+      // (y_triple<false> written out: with the weight formed before e^y the compiler schedules otherwise)
       const QuadSetup& sr = slots[wr].s;
 #pragma unroll
       for (int b = 0; b < YB; ++b) {
         const int j = base + b * kWaveSize + lane2;
-        const int jj = j < n ? j : n - 1;
+        const int jj = j < n ? j : n - 1;  // tail lanes recompute the last node with weight 0
         yv[b] = y_node(sr, jj);
-        ey[b] = exp_sc(pymax(pymin(yv[b], 50.0), -50.0));
+        ey[b] = exp_y<false>(yv[b]);
         wt[b] = j < n ? y_weight(sr, jj, yv[b]) : 0.0;
       }
     }
-#if LZQ_ACC_LDS
     double acc = slots[wr].acc[lane2];
-#endif
 #pragma unroll
     for (int b = 0; b < YB; ++b) {
-#if !LZQ_YFACT_EARLY
       const YFactors f =
           y_factors(slots[wr].s, yv[b], ey[b], wt[b], [&](double yy) { return win_eval<kLeanHere, Win>(slots[wr], yy); });
-#else
-      const YFactors& f = fy[b];
-#endif
       acc = __builtin_fma(f.w, integrand_from(f, F[b]), acc);
     }
-#if LZQ_ACC_LDS
     slots[wr].acc[lane2] = acc;
-#endif
   }
-#if LZQ_ACC_LDS
   if constexpr (kLeanHere) return wave_sum_rederived(slots[w].acc[lane_id()]);
   else return wave_sum(slots[w].acc[lane_id()]);
-#else
-  return wave_sum(acc);
-#endif
 }
 
 // fpy:372-384 (fast path) + fpy:413-417, split around the quadrature: epilogue_pre forms every
@@ -1318,9 +1157,7 @@ __device__ __forceinline__ lzq_yield epilogue_finish(const EpiPre& e, double YB)
 struct WaveSlot {
   QuadSetup s;
   EpiPre e;
-#if LZQ_ACC_LDS
   double acc[kWaveSize];  // per-lane running sums of yb_wave
-#endif
 };
 
 // Park the (wave-uniform) setup and epilogue inputs in the wave's slot.  Lane 0 writes; LDS

@@ -20,9 +20,7 @@ __device__ __forceinline__ double window_W(const WinParams& p, int32_t kind, dou
 struct WinWaveSlot {
   QuadSetup s;
   EpiPre e;
-#if LZQ_ACC_LDS
   double acc[kWaveSize];
-#endif
   WinParams win;
 };
 

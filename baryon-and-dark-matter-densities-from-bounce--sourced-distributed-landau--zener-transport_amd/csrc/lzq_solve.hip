@@ -35,9 +35,7 @@ namespace lzq {
 struct SolveWaveSlot {
   QuadSetup s;
   EpiPre e;
-#if LZQ_ACC_LDS
   double acc[kWaveSize];
-#endif
   WinParams win;
   SolveState st;     // the rule's state
   lzq_yield rec[2];  // the records of the bracket's lower and upper end

@@ -146,6 +146,32 @@ def test_build_inputs_cover_every_include():
     assert "lzq_superadiabatic.h" in b.HEADERS
 
 
+def test_build_variants_refuses_a_name_no_source_reads():
+    """tools/build_variants.py takes a define only if csrc/ has an `#ifndef` (or, for a debug switch
+    without a default, an `#ifdef`) for it: its own GRID and CONFIGS pass, the tuning parameters, the
+    five pinned z-sum switches and the switches its users' docstrings name pass, and a name that no
+    source reads is refused by name instead of building the default library again."""
+    import sys
+    import pytest
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tools"))
+    try:
+        import build_variants as bv
+    finally:
+        sys.path.pop(0)
+    bv.check_names([bv.GRID, *bv.CONFIGS])
+    bv.check_names([{"LZQ_KUNROLL": 4, "LZQ_MIN_WAVES": 4}, {"LZQ_TABBITS": 12}, {"LZQ_BLOCK": 256, "LZQ_YB": 2},
+                    {"LZQ_SQFORM": 0, "LZQ_POLYDEG": 3}, {"LZQ_PROF_PAIR": 0}, {"LZQ_ODE_COOP_DEBUG": 1},
+                    {n: 0 for n in ("LZQ_ZERO_SEG", "LZQ_DEAD_SEG", "LZQ_FROZEN_SEG", "LZQ_GROUP_SEG", "LZQ_PASS_LEAN")}])
+    with pytest.raises(SystemExit, match="LZQ_NO_SUCH_SWITCH"):
+        bv.check_names([{"LZQ_KUNROLL": 4}, {"LZQ_NO_SUCH_SWITCH": 1}])
+    with pytest.raises(SystemExit, match="LZQ_NO_SUCH_SWITCH"):   # the command line is checked before anything is built
+        argv, sys.argv = sys.argv, ["build_variants.py", "LZQ_YB=2,LZQ_NO_SUCH_SWITCH=1"]
+        try:
+            bv.main()
+        finally:
+            sys.argv = argv
+
+
 def test_build_stamp_tracks_content():
     """inputs_hash() is a content hash: it changes with a header's bytes (not its mtime), and the
     stamp written by build() is what up_to_date() compares."""

@@ -1,5 +1,5 @@
-"""The uniform-entry segments of the dense z-sum (csrc/lzq_quad.h zsum_dispatch / zsum_uniform,
-LZQ_UNIFORM_SEG), on the CPU.  tests/zsum_segments_host.cpp compiles the LZQ_HD functions of
+"""The uniform-entry segments of the dense z-sum (csrc/lzq_quad.h zsum_dispatch / zsum_uniform),
+on the CPU.  tests/zsum_segments_host.cpp compiles the LZQ_HD functions of
 csrc/lzq_exp2.h that the device code itself calls -- the segment predicates, the batch search, the
 segment's table value and the uniform node -- and evaluates a 64-lane pass twice: with the
 segmented dispatch, and with the single general loop (lzq::exp2_tab_scaled at every node).  The

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The share of the headline kernel's (pass, z-node) pairs that run the uniform-entry loop
-(csrc/lzq_quad.h zsum_uniform, LZQ_UNIFORM_SEG) on the C2 workload, counted on the host.
+(csrc/lzq_quad.h zsum_uniform) on the C2 workload, counted on the host.
 
 Every C2 point has the same y grid and the same c, so the 125 passes of one point are the whole
 grid.  The passes are planned by tests/zsum_dead_segment_host.cpp, i.e. by the LZQ_HD predicates and
