@@ -148,19 +148,21 @@ FT_AXES = [("m_chi_GeV", np.logspace(-1, 3, 64))]   # not a field of the z-sums:
 
 
 class FTable:
-    """lzq_sweep_grid_ztables / _from_ztables / lzq_sweep_grid through the raw ABI on FT_CFG x FT_AXES."""
+    """lzq_sweep_grid_ztables / _from_ztables / lzq_sweep_grid through the raw ABI on cfg x axes at n_y nodes
+    (FT_CFG x FT_AXES at LZQ_NY_MIN unless given; tests/test_gpu_yquad.py reads its cases' F from it)."""
 
-    def __init__(self, eng, nz, z_max):
+    def __init__(self, eng, nz, z_max, cfg=None, axes=None, n_y=NY_MIN):
         nat, cfgm = pkg("_native"), pkg("config")
-        self.eng, self.nat, self.nz, self.z_max = eng, nat, nz, z_max
-        self.base = cfgm.to_ctypes_point(cfgm.to_point(full_cfg(FT_CFG)))
-        self.vals = [torch.as_tensor(np.asarray(v, dtype=np.float64), device=eng.device) for _, v in FT_AXES]
-        self.arr = (nat.LzqAxis * len(FT_AXES))()
-        for a, ((name, _), t) in enumerate(zip(FT_AXES, self.vals)):
+        axes = FT_AXES if axes is None else axes
+        self.eng, self.nat, self.nz, self.z_max, self.n_y, self.axes = eng, nat, nz, z_max, n_y, axes
+        self.base = cfgm.to_ctypes_point(cfgm.to_point(full_cfg(FT_CFG if cfg is None else cfg)))
+        self.vals = [torch.as_tensor(np.asarray(v, dtype=np.float64), device=eng.device) for _, v in axes]
+        self.arr = (nat.LzqAxis * len(axes))()
+        for a, ((name, _), t) in enumerate(zip(axes, self.vals)):
             self.arr[a].field, self.arr[a].n, self.arr[a].values = nat.FIELD[name], t.numel(), t.data_ptr()
-        self.need = eng.lib.lzq_sweep_grid_reuse_workspace(self.arr, len(FT_AXES), NY_MIN)
-        assert self.need == NY_MIN + HDR            # one table
-        self.n = len(FT_AXES[0][1])
+        self.need = eng.lib.lzq_sweep_grid_reuse_workspace(self.arr, len(axes), n_y)
+        assert self.need == n_y + HDR               # one table
+        self.n = len(axes[0][1])
 
     def stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.eng.device).cuda_stream)
@@ -168,7 +170,7 @@ class FTable:
     def table(self):
         work = torch.full((self.need,), float("nan"), dtype=torch.float64, device=self.eng.device)
         with torch.cuda.device(self.eng.device):
-            self.nat.check(self.eng.lib.lzq_sweep_grid_ztables(ctypes.byref(self.base), self.arr, len(FT_AXES), NY_MIN,
+            self.nat.check(self.eng.lib.lzq_sweep_grid_ztables(ctypes.byref(self.base), self.arr, len(self.axes), self.n_y,
                                                                self.nz, self.z_max, ctypes.c_void_p(work.data_ptr()),
                                                                self.need, self.stream()), self.eng.lib)
         return work
@@ -177,7 +179,7 @@ class FTable:
         out = torch.empty((self.n, 6), dtype=torch.float64, device=self.eng.device)
         with torch.cuda.device(self.eng.device):
             self.nat.check(self.eng.lib.lzq_sweep_grid_from_ztables(
-                ctypes.byref(self.base), self.arr, len(FT_AXES), 0, self.n, NY_MIN, self.nz, self.z_max, None,
+                ctypes.byref(self.base), self.arr, len(self.axes), 0, self.n, self.n_y, self.nz, self.z_max, None,
                 ctypes.c_void_p(work.data_ptr()), self.need, ctypes.c_void_p(out.data_ptr()), self.stream()),
                 self.eng.lib)
         return out.cpu().numpy()
@@ -185,7 +187,7 @@ class FTable:
     def dense(self):
         out = torch.empty((self.n, 6), dtype=torch.float64, device=self.eng.device)
         with torch.cuda.device(self.eng.device):
-            self.nat.check(self.eng.lib.lzq_sweep_grid(ctypes.byref(self.base), self.arr, len(FT_AXES), 0, self.n, NY_MIN,
+            self.nat.check(self.eng.lib.lzq_sweep_grid(ctypes.byref(self.base), self.arr, len(self.axes), 0, self.n, self.n_y,
                                                        self.nz, self.z_max, None, ctypes.c_void_p(out.data_ptr()),
                                                        self.stream()), self.eng.lib)
         return out.cpu().numpy()

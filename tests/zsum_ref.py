@@ -250,9 +250,10 @@ ODE_WINDOW = {"T_min_over_Tp": 0.78, "T_max_over_Tp": 0.90}   # y from 32 down t
 ODE_NT = 200                                                  # knots: not a multiple of 64
 
 
-def ft_ygrid(c):
-    """numpy restatement of quad_setup's y-grid and c for the config c at n_y = LZQ_NY_MIN
-    (csrc/lzq_quad.h; fpy:234-247): (y_lo, y_hi, cneg, ys)."""
+def ft_ygrid(c, n_y=NY_MIN):
+    """numpy restatement of quad_setup's y-grid and c for the config c at n_y nodes (at least
+    LZQ_NY_MIN, fpy:246; csrc/lzq_quad.h; fpy:234-247): (y_lo, y_hi, cneg, ys)."""
+    n = max(int(n_y), NY_MIN)
     Tp, B = c["T_p_GeV"], c["beta_over_H"]
 
     def y_of_T(T):
@@ -261,8 +262,8 @@ def ft_ygrid(c):
 
     y_lo = max(y_of_T(c["T_max_over_Tp"] * Tp), -80.0)
     y_hi = min(y_of_T(c["T_min_over_Tp"] * Tp), 50.0)
-    step = (y_hi - y_lo) / float(NY_MIN - 1)
-    ys = np.arange(NY_MIN, dtype=np.float64) * step + y_lo
+    step = (y_hi - y_lo) / float(n - 1)
+    ys = np.arange(n, dtype=np.float64) * step + y_lo
     ys[-1] = y_hi
     return y_lo, y_hi, -(c["I_p"] / 6.0), ys
 
