@@ -95,6 +95,21 @@ WINDOW_DTYPE = np.dtype([("kind", "<i4"), ("table", "<i4")] + [(n, "<f8") for n 
 assert ctypes.sizeof(LzqWindow) == 48 == WINDOW_DTYPE.itemsize and ctypes.sizeof(LzqWindowTables) == 24
 
 
+FK_POWER = 0  # enum lzq_fk_kind
+FK_KINDS = {"power": FK_POWER}
+FK_P_MAX = 8.0  # LZQ_FK_P_MAX
+FK_TABLE_HEADER = 6  # LZQ_FK_TABLE_HEADER
+FK_NZ_CONT = -1  # LZQ_FK_NZ_CONT
+
+
+class LzqFk(ctypes.Structure):  # struct lzq_fk: the momentum kernel F(k) of a point's LZ probability
+    _fields_ = [("kind", ctypes.c_int32), ("pad", ctypes.c_int32), ("p", ctypes.c_double), ("v_ref", ctypes.c_double)]
+
+
+FK_DTYPE = np.dtype([("kind", "<i4"), ("pad", "<i4"), ("p", "<f8"), ("v_ref", "<f8")])
+assert ctypes.sizeof(LzqFk) == 24 == FK_DTYPE.itemsize
+
+
 class LzqSolve(ctypes.Structure):  # struct lzq_solve: one parameter solved per grid point for a target yield
     _fields_ = [("field", ctypes.c_int32), ("target_field", ctypes.c_int32), ("lo", ctypes.c_double),
                 ("hi", ctypes.c_double), ("target", ctypes.c_double), ("xtol", ctypes.c_double),
@@ -196,6 +211,8 @@ EXPORTS = ("lzq_abi_version", "lzq_last_error", "lzq_init", "lzq_zgrid_init", "l
            "lzq_cont_tables", "lzq_aov_cont_host", "lzq_aov_batch_cont", "lzq_sweep_grid_ztables_cont",
            "lzq_sweep_grid_from_ztables_cont", "lzq_sweep_grid_cont", "lzq_yields_batch_cont",
            "lzq_sweep_grid_solve_cont",
+           "lzq_fk_check_host", "lzq_fk_pbar_host", "lzq_fk_pbar_batch", "lzq_fk_nodes", "lzq_fk_table_stride",
+           "lzq_fk_tables", "lzq_yields_batch_reuse_fk",
            "lzq_lz_propagate", "lzq_lz_propagate_v", "lzq_ode_tables", "lzq_ode_integrate", "lzq_ode_integrate_shared", "lzq_ode_rows", "lzq_ode_integrate_rows", "lzq_ode_integrate_tp", "lzq_ode_quadrature", "lzq_ode_batch",
            "lzq_ode_aov_T", "lzq_ode_rhs", "lzq_profile_splines", "lzq_profile_crossings",
            "lzq_lz_propagate_profile",
@@ -288,6 +305,14 @@ def load(path: str | None = None):
     L.lzq_yields_batch_cont.argtypes = [vp, i64, i32, d, vp, vp, vp, i64, vp, i64, vp, P(LzqWindowTables), vp, vp]
     L.lzq_sweep_grid_solve_cont.argtypes = [P(LzqPoint), P(LzqWindow), P(LzqAxis), i32, P(LzqSolve), i64, i64, i32, d,
                                             vp, vp, i64, P(LzqWindowTables), vp, vp, vp]
+    L.lzq_fk_check_host.argtypes = [vp, vp, i64]
+    L.lzq_fk_pbar_host.argtypes = [P(LzqFk), i32, vp, vp, i64, vp]
+    L.lzq_fk_pbar_batch.argtypes = [P(LzqFk), i32, vp, vp, i64, vp, vp]
+    L.lzq_fk_nodes.argtypes = [P(d), P(d), P(d), P(i32)]
+    L.lzq_fk_table_stride.argtypes = [i32]
+    L.lzq_fk_tables.argtypes = [vp, vp, vp, vp, i64, i32, vp, i64, vp, vp]
+    L.lzq_yields_batch_reuse_fk.argtypes = [vp, i64, i32, i32, d, vp, vp, vp, vp, i64, vp, vp, i64, vp,
+                                            P(LzqWindowTables), vp, vp]
     L.lzq_lz_propagate.argtypes = [vp, vp, vp, i64, i32, d, d, i32, vp, vp]
     L.lzq_lz_propagate_v.argtypes = [vp, vp, vp, vp, i64, i32, d, i32, vp, vp]
     L.lzq_ode_tables.argtypes = [vp, i64, vp, vp, i32, i32, d, vp, vp, i64, vp, vp]
@@ -330,6 +355,7 @@ def load(path: str | None = None):
     L.lzq_post_state_bytes.restype = ctypes.c_int64
     L.lzq_obs_state_bytes.restype = ctypes.c_int64
     L.lzq_rank_state_bytes.restype = ctypes.c_int64
+    L.lzq_fk_table_stride.restype = ctypes.c_int64
     if path is None:
         _lib = L
     return L

@@ -13,7 +13,7 @@ import torch
 
 import logging
 
-from . import _native, fit as _fit, solve as _solve, window as _window
+from . import _native, fit as _fit, fk as _fk, solve as _solve, window as _window
 from .config import to_aov, to_ctypes_aov, to_ctypes_ode, to_ctypes_point, to_point
 
 _log = logging.getLogger("lzq")
@@ -210,7 +210,7 @@ class Engine:
     # -- fpy:231-267 + epilogue ----------------------------------------------------------------
     def yields(self, points, n_y: int = 8000, T_lo=None, T_hi=None, P=None, reuse: bool = False,
                nz: int = _native.LZQ_NZ, z_max: float = _native.LZQ_Z_MAX, aov=None, window=None,
-               window_tables=None, continuum: bool = False) -> torch.Tensor:
+               window_tables=None, continuum: bool = False, fk=None, fk_delta=None) -> torch.Tensor:
         """points: POINT_DTYPE numpy array or a device byte tensor from points_to_device.
         Returns (n, 6) float64 device tensor in YIELD_FIELDS order.
         reuse: lzq_yields_batch_reuse -- points equal in _native.ZSUM_KEY share one table of
@@ -227,7 +227,26 @@ class Engine:
         continuum: the z-sums on the continuum z rule of z_max (include/lzq.h "A/V in the continuum
         limit"; nz is not read).  Always through shared z-sum tables, one per distinct _native.ZSUM_KEY
         (`reuse`'s grouping), in chunks where the tables of a batch exceed REUSE_MAX_BYTES; main()'s
-        window only, and not with `aov`."""
+        window only, and not with `aov`.
+        fk: the momentum kernel F(k) of the LZ probability (include/lzq.h lzq_fk; see fk.to_fk): one block
+        for all points or n records.  P-bar(m/T(y)) then stands inside the y-integral in place of the
+        constant P (csrc/lzq_fk.h); fk_delta is delta_0 per point (PAPER eq. (8) at F = 1; one value or n),
+        by default -log1p(-P)/(2 pi) from each point's P_chi_to_B.  Always from shared z-sum tables, the
+        linspace grid's or with `continuum` the continuum rule's; `points` is then a host array.  With a
+        window or main()'s; not with `aov`, `P`, T_lo or T_hi."""
+        if fk is None and fk_delta is not None:
+            raise ValueError("yields: fk_delta without fk")
+        if fk is not None:
+            if aov is not None:
+                raise ValueError("yields: a momentum kernel (fk) together with a replaced A/V kernel (aov) is not "
+                                 "supported")
+            if T_lo is not None or T_hi is not None or P is not None:
+                raise ValueError("yields: fk runs from shared z-sum tables (main()'s T range) and takes delta_0, "
+                                 "not a P override")
+            if isinstance(points, torch.Tensor):
+                raise ValueError("yields: fk needs the points as a host POINT_DTYPE array (the class grouping is "
+                                 "done on the host)")
+            return self._yields_fk(points, int(n_y), nz, z_max, continuum, fk, fk_delta, window, window_tables)
         if continuum:
             if aov is not None:
                 raise ValueError("yields: a replaced A/V kernel (aov) together with the continuum z rule is not supported")
@@ -287,6 +306,100 @@ class Engine:
                                                         _vp(d_aov), _vp(out), self._stream()))
                 self._keepalive_aov = d_aov
                 self.last_yields_path = "dense"
+        return out
+
+    def pbar(self, block, mu, delta, stats=_native.FERMION) -> torch.Tensor:
+        """P-bar(mu) of one momentum-kernel block at delta_0 = delta on the device (lzq_fk_pbar_batch):
+        the R-table kernel's evaluation alone.  mu and delta broadcast against each other."""
+        rec = _fk.to_fk(block)
+        _fk.check(rec)
+        m, d = torch.broadcast_tensors(self._f64(mu), self._f64(delta))
+        m, d = m.contiguous().reshape(-1), d.contiguous().reshape(-1)
+        out = torch.empty_like(m)
+        blk = _native.LzqFk.from_buffer_copy(rec.tobytes())
+        with torch.cuda.device(self.device):
+            self._check(self.lib.lzq_fk_pbar_batch(ctypes.byref(blk), _fk.stats_code(stats), _vp(m), _vp(d), m.numel(),
+                                                   _vp(out), self._stream()))
+        return out
+
+    def fk_tables(self, d_pts, d_delta, d_fk, rep, n_y: int, with_mu: bool = False):
+        """The R tables of the classes whose first points are rep (lzq_fk_tables): a float64 device
+        tensor (n_classes, lzq_fk_table_stride(n_y)) and, with_mu, the mu_j the kernel formed
+        (n_classes, n + 1)."""
+        stride = int(self.lib.lzq_fk_table_stride(int(n_y)))
+        nc = int(rep.numel())
+        R = torch.empty((nc, stride), dtype=torch.float64, device=self.device)
+        mu = torch.empty((nc, stride - _native.FK_TABLE_HEADER), dtype=torch.float64, device=self.device) \
+            if with_mu else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.lzq_fk_tables(_vp(d_pts), _vp(d_delta), _vp(d_fk), _vp(rep), nc, int(n_y), _vp(R),
+                                               R.numel(), _vp(mu), self._stream()))
+        return (R, mu) if with_mu else R
+
+    def _yields_fk(self, points, n_y, nz, z_max, continuum, fk, fk_delta, window, window_tables) -> torch.Tensor:
+        """Engine.yields(fk=...): per chunk of points whose z-sum tables fit REUSE_MAX_BYTES, the z-sum
+        tables (lzq_yields_batch_reuse / _cont, whose own yields are overwritten), the R tables of the
+        chunk's classes (lzq_fk_tables) and the integration (lzq_yields_batch_reuse_fk)."""
+        if continuum:
+            z_max = _native.cont_z_max(z_max)
+        else:
+            nz, z_max = _native.zgrid(nz, z_max)
+        pts = np.ascontiguousarray(points, dtype=_native.POINT_DTYPE).reshape(-1)
+        n = pts.size
+        fks = _fk.to_fks(fk, n)
+        delta = _fk.point_delta(pts, fk_delta)
+        _fk.check(fks, delta)
+        d_wt = None
+        win_rec = None
+        if window is not None:
+            d_wt = self.window_tables_to_device(window_tables)
+            win_rec = _window.to_windows(window, n)
+            d_wt.check_blocks(win_rec)
+        elif window_tables is not None:
+            raise ValueError("yields: window_tables without a window")
+        out = torch.empty((n, 6), dtype=torch.float64, device=self.device)
+        stride = max(n_y, 2000) + _native.REUSE_TABLE_HEADER
+        cap = max(1, REUSE_MAX_BYTES // (stride * 8))
+        self._ztab_key = None   # the grid tables in _zwork are overwritten
+        self.last_yields_path = "tables"
+        self.last_fk_classes = 0
+        lo = 0
+        with torch.cuda.device(self.device):
+            while lo < n:
+                hi = min(lo + cap, n)
+                m = hi - lo
+                d_pts = self.points_to_device(pts[lo:hi])
+                g = table_groups(d_pts, m, _ZSUM_WORDS)
+                if g is None:   # one point, or sharing would not pay: a table per point
+                    ar = torch.arange(m, dtype=torch.int64, device=self.device)
+                    g = (ar, ar)
+                rep, inv = g
+                need = rep.numel() * stride
+                if self._zwork is None or self._zwork.numel() < need:
+                    self._zwork = torch.empty(need, dtype=torch.float64, device=self.device)
+                idx = inv.to(torch.int32)
+                if continuum:
+                    self._check(self.lib.lzq_yields_batch_cont(
+                        _vp(d_pts), m, n_y, z_max, None, _vp(rep), _vp(idx), rep.numel(), _vp(self._zwork),
+                        self._zwork.numel(), None, None, _vp(out[lo:hi]), self._stream()))
+                else:
+                    self._check(self.lib.lzq_yields_batch_reuse(
+                        _vp(d_pts), m, n_y, nz, z_max, None, _vp(rep), _vp(idx), rep.numel(), _vp(self._zwork),
+                        self._zwork.numel(), _vp(out[lo:hi]), self._stream()))
+                crep, cls = _fk.class_groups(pts[lo:hi], delta[lo:hi], fks[lo:hi])
+                d_delta = self._f64(delta[lo:hi])
+                d_fk = _to_device_bytes(fks[lo:hi], self.device)
+                d_crep = torch.as_tensor(crep, device=self.device)
+                d_cls = torch.as_tensor(cls, device=self.device)
+                R = self.fk_tables(d_pts, d_delta, d_fk, d_crep, n_y)
+                d_win = None if win_rec is None else _to_device_bytes(win_rec[lo:hi], self.device)
+                self._check(self.lib.lzq_yields_batch_reuse_fk(
+                    _vp(d_pts), m, n_y, _native.FK_NZ_CONT if continuum else nz, z_max, _vp(d_delta), _vp(d_fk),
+                    _vp(idx), _vp(self._zwork), need, _vp(d_cls), _vp(R), R.numel(), _vp(d_win),
+                    d_wt.arg if d_wt is not None else None, _vp(out[lo:hi]), self._stream()))
+                self._keepalive_fk = (d_pts, rep, idx, d_delta, d_fk, d_crep, d_cls, R, d_win, d_wt)
+                self.last_fk_classes += int(crep.size)
+                lo = hi
         return out
 
     def _yields_cont(self, d_pts, n, n_y, z_max, Pv, d_win, d_wt, out) -> None:

@@ -167,6 +167,31 @@ class WindowSpec:
         return cls(d, None if t is None else t.u.tolist(), None if t is None else t.W.tolist())
 
 
+# sweep axes over the fields of the spec's momentum-kernel block (include/lzq.h lzq_fk)
+FK_AXES = {"fk_p": "p", "fk_v_ref": "v_ref"}
+LZ_AXES = ("delta_LZ", "m_mix", "dprime")
+
+
+@dataclass
+class FkSpec:
+    """The momentum kernel F(k) of every grid point's LZ probability (PAPER §10 step 1; include/lzq.h
+    lzq_fk): `block` is the base block ({"kind": "power", "p", "v_ref"}; fk.to_fk), which the FK_AXES
+    sweep.  P-bar(m/T(y)) then stands inside the y-integral (Engine.yields(fk=)); delta_0 of a point is
+    PAPER eq. (8) at F = 1 from the delta_LZ / m_mix / dprime axes, computed on the host, else the
+    delta_0 of the base's P_chi_to_B."""
+    block: dict
+
+    def to_json(self) -> dict:
+        return dict(self.block)
+
+    @classmethod
+    def from_json(cls, d: dict) -> "FkSpec":
+        from . import fk as _fk
+        d = dict(d)
+        _fk.check(_fk.to_fk(d))   # unknown fields / kinds raise in to_fk
+        return cls(d)
+
+
 ODE_MAX_STEPS = 1 << 26   # a sweep's default cap on one ODE point's fixed Radau steps (LZQ_ODE_TOO_MANY_STEPS beyond)
 
 
@@ -193,6 +218,7 @@ class SweepSpec:
     # "linspace": the reference's (nz, z_max) grid; "continuum": the converged z-integral on the
     # continuum z rule of z_max (include/lzq.h "A/V in the continuum limit"; nz is then not read)
     z_rule: str = "linspace"
+    fk: Optional[FkSpec] = None   # None: the paper's F = 1 (one P per point)
 
     @property
     def continuum(self) -> bool:
@@ -232,6 +258,8 @@ class SweepSpec:
             d["solve"] = _solve.normalize(self.solve)
         if self.z_rule != "linspace":
             d["z_rule"] = self.z_rule
+        if self.fk is not None:
+            d["fk"] = self.fk.to_json()
         return d
 
     def axis_values(self, start: int, count: int, device) -> dict:
@@ -300,6 +328,8 @@ def grid_records(spec: "SweepSpec", start: int, count: int, engine=None):
             continue          # P comes from the profile (profile_P)
         elif name in WINDOW_AXES:
             continue          # a field of the point's window block (window_records)
+        elif name in FK_AXES:
+            continue          # a field of the point's momentum-kernel block (fk_records)
         elif name in ODE_FIELDS:
             ods[name] = v if name != "deplete_DM_from_source" else (v != 0).astype(np.int32)
         elif name == "Y_chi_init":
@@ -336,6 +366,33 @@ def window_records(spec: "SweepSpec", start: int, count: int) -> np.ndarray:
     return rec
 
 
+def fk_records(spec: "SweepSpec", start: int, count: int, pts: np.ndarray) -> tuple:
+    """(FK_DTYPE blocks, delta_0) of grid indices [start, start+count): the spec's base block with the
+    FK_AXES values decoded in C order, like grid_records (whose records `pts` are: v_w enters eq. (8));
+    delta_0 from the delta_LZ or the m_mix / dprime axes by PAPER eq. (8) at F = 1 on the host, else
+    from the records' P_chi_to_B."""
+    from . import fk as _fk
+    rec = np.repeat(_fk.to_fk(spec.fk.block), count)
+    idx = np.arange(start, start + count, dtype=np.int64)
+    stride = 1
+    lz = {}
+    for name, vals in reversed(spec.axes):
+        if name in FK_AXES or name in LZ_AXES:
+            v = np.asarray(vals, dtype=np.float64)[(idx // stride) % len(vals)]
+            if name in FK_AXES:
+                rec[FK_AXES[name]] = v
+            else:
+                lz[name] = v
+        stride *= len(vals)
+    if "m_mix" in lz:
+        delta = lz["m_mix"] * lz["m_mix"] / (2.0 * np.maximum(pts["v_w"], 1e-12) * np.abs(lz["dprime"]))
+    elif "delta_LZ" in lz:
+        delta = lz["delta_LZ"]
+    else:
+        delta = _fk.delta_from_P(pts["P_chi_to_B"])
+    return rec, np.ascontiguousarray(delta, dtype=np.float64)
+
+
 def _axis_from_json(a: dict) -> Tuple[str, np.ndarray]:
     if "values" in a:
         v = np.asarray(a["values"], dtype=np.float64)
@@ -346,7 +403,7 @@ def _axis_from_json(a: dict) -> Tuple[str, np.ndarray]:
     else:
         raise ValueError(f"axis {a!r} needs values / linspace / logspace")
     if a["field"] not in _native.FIELD and a["field"] not in ODE_FIELDS and a["field"] not in PROFILE_FIELDS and \
-            a["field"] not in WINDOW_AXES:
+            a["field"] not in WINDOW_AXES and a["field"] not in FK_AXES:
         raise ValueError(f"unknown sweep field {a['field']!r}")
     return a["field"], v
 
@@ -380,8 +437,10 @@ def spec_from_json(d: dict) -> SweepSpec:
     # 0 means "no cap", as --ode-max-steps 0 on the command line does (one meaning in both places)
     spec = SweepSpec(d.get("name", "custom"), base, axes, int(d.get("n_y", 8000)), d.get("notes", ""), cr, method, prof,
                      nz, z_max, None if ms is None or int(ms) == 0 else int(ms), win,
-                     _solve.normalize(d["solve"]) if d.get("solve") else None, d.get("z_rule", "linspace"))
+                     _solve.normalize(d["solve"]) if d.get("solve") else None, d.get("z_rule", "linspace"),
+                     FkSpec.from_json(d["fk"]) if d.get("fk") is not None else None)
     check_z_rule(spec)
+    check_fk_spec(spec)
     check_window_spec(spec)
     check_solve_spec(spec)
     return spec
@@ -418,6 +477,37 @@ def check_solve_spec(spec: SweepSpec) -> None:
     if spec.window is not None and window_axes_collide(spec):
         raise ValueError("a 'solve' section on a spec whose window axes collide (the grid entry points refuse them)")
     _solve.check(sv, [n for n, _ in grid_axes_for_kernel(spec)], None if spec.window is None else spec.window.block)
+
+
+def check_fk_spec(spec: SweepSpec) -> None:
+    """An "fk" section the sweep cannot run, as a ValueError: fk axes without the section, a spec whose
+    points take the ODE fallback, whose P comes from crossings or a profile (P-bar needs delta_0, not a
+    P), or that carries a solve (the solve kernels take no momentum kernel); m_mix without dprime; and
+    every block of the fk axes that the library refuses."""
+    names = [n for n, _ in spec.axes]
+    if spec.fk is None:
+        if any(n in FK_AXES for n in names):
+            raise ValueError(f"axes {tuple(FK_AXES)} need an 'fk' section")
+        return
+    if is_ode_spec(spec):
+        raise ValueError("an 'fk' section on a spec whose points take the ODE fallback (sigma_v / Gamma_wash / "
+                         "depletion): the ODE path takes no momentum kernel")
+    if spec.crossings is not None or spec.profile is not None:
+        raise ValueError("an 'fk' section on a spec whose P comes from crossings or a profile: P-bar is built "
+                         "from delta_0 (the delta_LZ or m_mix / dprime axes)")
+    if spec.solve is not None:
+        raise ValueError("an 'fk' section next to a 'solve' section: the solve kernels take no momentum kernel")
+    if ("m_mix" in names) != ("dprime" in names):
+        raise ValueError("an 'fk' spec takes delta_0 from a delta_LZ axis or from m_mix and dprime axes together")
+    from . import fk as _fk
+    for n, v in spec.axes:
+        if n in FK_AXES:
+            rec = np.repeat(_fk.to_fk(spec.fk.block), len(v))
+            rec[FK_AXES[n]] = np.asarray(v, dtype=np.float64)
+            try:
+                _fk.check(rec)
+            except _native.LzqError as e:
+                raise ValueError(f"axis {n!r}: {e}") from None
 
 
 def check_window_spec(spec: SweepSpec) -> None:
@@ -900,6 +990,21 @@ def make_compute(spec: SweepSpec, engine, reuse: bool = False, window_host_recor
     check_z_rule(spec)
     check_window_spec(spec)
     check_solve_spec(spec)
+    check_fk_spec(spec)
+    if spec.fk is not None:
+        # explicit host records (the device does not decode fk axes): each chunk's points, blocks and
+        # delta_0, through Engine.yields(fk=) -- shared z-sum tables, the R tables of the chunk's classes
+        d_tables = engine.window_tables_to_device(spec.window.host_tables()) if spec.window is not None else None
+
+        def compute_fk(s, n, out):
+            pts, _ = grid_records(spec, s, n, engine)
+            fks, delta = fk_records(spec, s, n, pts)
+            out.copy_(engine.yields(pts, n_y=spec.n_y, nz=spec.nz, z_max=spec.z_max, continuum=spec.continuum,
+                                    fk=fks, fk_delta=delta,
+                                    window=None if spec.window is None else window_records(spec, s, n),
+                                    window_tables=d_tables))
+            engine.last_reuse = engine.last_yields_path
+        return compute_fk
     if spec.solve is not None:
         # the inverse sweep: always from the shared z-sum tables (Engine.sweep(solve=)); the records at
         # the solutions go to `out`, the results ride back on the function (run_local collects them)

@@ -480,6 +480,74 @@ int lzq_sweep_grid_solve_cont(const lzq_point* base, const lzq_window* base_win,
                               const lzq_window_tables* d_tables, lzq_yield* d_out, lzq_solve_result* d_sol,
                               void* stream);
 
+/* ---- momentum-averaged LZ probability P-bar(T) from F(k) (PAPER §10 step 1) ---- */
+/* Everywhere above P_chi_to_B is one number per point that multiplies the quadrature from outside:
+ * PAPER eq. (8) with the placeholder F(k) = 1.  With a momentum kernel F the conversion probability
+ * depends on the particle's speed v = k/E in the plasma frame, and its average over the thermal flux
+ * on m/T, so it belongs inside the y-integral, Y_B = int g(y) P-bar(y) dy (csrc/lzq_fk.h holds the one
+ * definition that the host and the device build):
+ *
+ *   mu = m_chi/T(y), T(y) as the quadrature forms it;  t = (E - m)/T,  v = sqrt(t (t + 2 mu))/(t + mu)
+ *   omega(t)  = t (t + 2 mu) e^-t / (1 +- e^-mu e^-t)        + LZQ_FERMION, - LZQ_BOSON
+ *   P-bar(mu) = int omega(t) [-expm1(-2 pi delta_0 F(v))] dt / int omega(t) dt
+ *   F(v)      = (v_ref / v)^p                                 LZQ_FK_POWER; p = 0 is F = 1
+ *
+ * delta_0 >= 0 is eq. (8) at F = 1, one per point.  J(T), its relativistic / non-relativistic branch
+ * included, stays the reference's: only the constant P is replaced by the normalised average, so
+ * p = 0 gives P = 1 - e^(-2 pi delta_0) back up to rounding.  The t-integrals run on one fixed node
+ * table (350 nodes, rule error 3.6e-14 relative; numerator and denominator in node order with the same
+ * weights: delta_0 = +inf gives exactly 1 and delta_0 = 0 exactly +0).
+ * A block is refused (LZQ_EINVAL and a message from the host-side checks; NaN from a kernel that meets
+ * one in device memory) when its kind is unknown, p is NaN, < 0 or > LZQ_FK_P_MAX, or v_ref is NaN,
+ * <= 0 or > 1; a point when its delta_0 is NaN or < 0.  24 bytes. */
+enum lzq_fk_kind { LZQ_FK_POWER = 0 };
+#define LZQ_FK_P_MAX 8.0
+typedef struct lzq_fk {
+  int32_t kind; /* enum lzq_fk_kind */
+  int32_t pad;
+  double p, v_ref;
+} lzq_fk;
+/* Host-side check of n blocks and (delta0 non-NULL) n values of delta_0: every refusal above, the
+ * message naming the field.  No GPU. */
+int lzq_fk_check_host(const lzq_fk* fk, const double* delta0, int64_t n);
+/* The host build of the definition: out[i] = P-bar(mu[i]) at delta0[i] for one block and statistics
+ * (libm's exp, log, expm1).  mu NaN or < 0 is LZQ_EINVAL.  No GPU. */
+int lzq_fk_pbar_host(const lzq_fk* fk, int32_t stats, const double* mu, const double* delta0, int64_t n, double* out);
+/* Its device twin (device arrays; the device library's exp, log, expm1, <= 1 ulp each).  The block
+ * is checked on the host; a mu or delta_0 in device memory that is NaN or < 0 gives NaN. */
+int lzq_fk_pbar_batch(const lzq_fk* fk, int32_t stats, const double* d_mu, const double* d_delta0, int64_t n,
+                      double* d_out, void* stream);
+/* The host copy of the node table: *n nodes (set whenever non-NULL); t, w_exp = W e^-t, e = e^-t may
+ * be NULL (call once for *n).  No GPU. */
+int lzq_fk_nodes(double* t, double* w_exp, double* e, int32_t* n);
+/* R tables.  Points that agree in T_p_GeV, beta_over_H, T_min_over_Tp, T_max_over_Tp (the y-grid and
+ * T(y)), m_chi_GeV, stats, delta_0 and their block form a class and share one table of
+ * R_j = P-bar(m/T(y_j)), j < n = max(n_y, LZQ_NY_MIN): table c is made for point d_rep[c] (int64) with
+ * d_delta0[d_rep[c]] and d_fk[d_rep[c]], one wavefront per 64 y-nodes.  Layout: LZQ_FK_TABLE_HEADER
+ * key doubles, the n values R_j, then P-bar(m/T_p), the P_used of the class's records;
+ * d_R >= n_classes * lzq_fk_table_stride(n_y) doubles.  A class whose block or delta_0 is refused has
+ * NaN throughout.  d_mu (optional, same layout less the header: n_classes * (n + 1) doubles) receives
+ * the mu_j the kernel formed. */
+#define LZQ_FK_TABLE_HEADER 6
+int64_t lzq_fk_table_stride(int32_t n_y);
+int lzq_fk_tables(const lzq_point* d_points, const double* d_delta0, const lzq_fk* d_fk, const int64_t* d_rep,
+                  int64_t n_classes, int32_t n_y, double* d_R, int64_t r_doubles, double* d_mu, void* stream);
+/* Y_B = int g(y) P-bar(y) dy from shared tables: point i is integrated from its z-sum table
+ * d_table_index[i] of d_work (tables built for the same n_y and z grid by lzq_yields_batch_reuse,
+ * lzq_sweep_grid_ztables or their _cont forms; nz = LZQ_FK_NZ_CONT: the continuum rule of z_max) and
+ * from R table d_class[i] of d_R, both int32.  The per-y work is lzq_yields_batch_reuse's with P = 1
+ * and the window factor W(y_j) R_j; W is point i's block d_win[i] (d_tables as for
+ * lzq_yields_batch_window), or with d_win = NULL the point's Gaussian.  P_chi_to_B is not read;
+ * P_used is P-bar(m/T_p).  A point whose own y-grid, c, z grid, m, stats, delta_0 or block differ from
+ * its tables' headers gets NaN yields; a refused block or delta_0 gives NaN Y_B, rho_B, DM_over_B and
+ * P_used and reads no table. */
+#define LZQ_FK_NZ_CONT (-1)
+int lzq_yields_batch_reuse_fk(const lzq_point* d_points, int64_t n, int32_t n_y, int32_t nz, double z_max,
+                              const double* d_delta0, const lzq_fk* d_fk, const int32_t* d_table_index,
+                              const double* d_work, int64_t work_doubles, const int32_t* d_class, const double* d_R,
+                              int64_t r_doubles, const lzq_window* d_win, const lzq_window_tables* d_tables,
+                              lzq_yield* d_out, void* stream);
+
 /* The ODE entry points below take no window: their source term keeps the reference's Gaussian
  * (fpy:226-228).  Engine.ode and the facade's ODE operators raise when given another one.  Nor do they
  * take the continuum rule: lzq_ode_tables stays on the linspace grids. */
