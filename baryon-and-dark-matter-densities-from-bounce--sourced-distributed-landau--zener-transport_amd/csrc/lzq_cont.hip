@@ -196,13 +196,18 @@ int lzq::cont_grid_for(int dev, double z_max, const ZNode** zt, int32_t* nzp) {
   if (rc) return rc;
   const int32_t n = (int32_t)t->z.size() + 1;
   const int32_t np = (n + kKUnroll - 1) / kKUnroll * kKUnroll;
-  std::vector<ZNode> host(np);
+  // (the image of every z grid: the nodes, then their weights packed -- zimage_pack, lzq_exp2.h)
+  static_assert(sizeof(ZNode) == 2 * sizeof(double), "ZNode layout");
+  std::vector<double> image(zimage_doubles(np));
+  ZNode* host = reinterpret_cast<ZNode*>(image.data());
   host[0] = ZNode{0.0, 0.0};
   for (int32_t k = 1; k < np; ++k)
     host[k] = k < n ? ZNode{t->g4[k - 1], ldexp(t->omega[k - 1], -kOmegaBias)} : ZNode{t->g4[n - 2], 0.0};
-  ZNode* d = nullptr;
-  LZQ_HIP(hipMalloc(&d, host.size() * sizeof(ZNode)));
-  LZQ_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(ZNode), hipMemcpyHostToDevice));
+  zimage_pack(host, np);
+  void* dv = nullptr;
+  LZQ_HIP(hipMalloc(&dv, image.size() * sizeof(double)));
+  LZQ_HIP(hipMemcpy(dv, image.data(), image.size() * sizeof(double), hipMemcpyHostToDevice));
+  ZNode* d = static_cast<ZNode*>(dv);
   g_dev.push_back(DevEntry{dev, zb, d, np});
   *zt = d;
   *nzp = np;

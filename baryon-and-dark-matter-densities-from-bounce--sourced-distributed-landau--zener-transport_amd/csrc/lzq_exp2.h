@@ -387,6 +387,21 @@ LZQ_HD int seg_group_kind(int packed, int g) {
   return m;
 }
 
+// The packed omega' array of a z grid's device image (LZQ_ACC_FEED; lzq_quad.h's zsum_dead and zsum_held
+// read it).  The image of a grid of nzp padded nodes is nzp {g4, omega'} pairs, then the same nzp weights
+// once more as contiguous doubles: a loop that needs omega' alone touches one 64-byte line per 8-node
+// batch there, not the two of the interleaved pairs.  One layout for every producer (the default grid,
+// whose exp table follows the packed array; a runtime grid; the continuum grid), so the array sits at a
+// fixed place seen from the nodes and no kernel takes an argument for it.  zimage_doubles: the image's
+// size; zimage_pack: fills the packed part from the nodes, the weights' own bits, padding +0 included.
+LZQ_HD int zimage_doubles(int nzp) { return 3 * nzp; }
+LZQ_HD const double* zimage_omega(const void* nodes, int nzp) { return static_cast<const double*>(nodes) + 2 * nzp; }
+template <class Node>
+static inline void zimage_pack(Node* nodes, int nzp) {
+  double* packed = reinterpret_cast<double*>(nodes) + 2 * nzp;
+  for (int k = 0; k < nzp; ++k) packed[k] = nodes[k].omega;
+}
+
 // First node k2 in [0, kend], a multiple of `unroll` (which divides kend), with pred(g4(k2)); pred
 // must be monotone in k (false ... false true ... true); kend if it holds at no batch start.
 template <class Pred, class G4>

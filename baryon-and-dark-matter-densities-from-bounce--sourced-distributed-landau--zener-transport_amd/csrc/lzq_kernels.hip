@@ -303,14 +303,17 @@ namespace {
 thread_local char g_err[512] = "";
 std::mutex g_mu;
 constexpr int kMaxDevices = 64;
-// per device: the default grid's [LZQ_NZ] ZNode followed by the kTabN-entry exp table
+// per device: the default grid's image ([LZQ_NZ] ZNode, then their LZQ_NZ weights packed: zimage_doubles,
+// lzq_exp2.h) followed by the kTabN-entry exp table
 lzq::ZNode* g_dev_tab[kMaxDevices] = {nullptr};
 uint64_t g_exp2tab[lzq::kTabN];  // lzq::tab_entry_bits layout
 bool g_exp_ready = false;
 int g_exp_variant = lzq::kExpTable;
 int g_truncate = 0;  // LZQ_TUNE_TRUNCATE
 
-const double* exp_table(int dev) { return reinterpret_cast<const double*>(g_dev_tab[dev] + LZQ_NZ); }
+const double* exp_table(int dev) {
+  return reinterpret_cast<const double*>(g_dev_tab[dev]) + lzq::zimage_doubles(LZQ_NZ);
+}
 
 int fail(int code, const char* fmt, ...) {
   va_list ap;
@@ -421,6 +424,15 @@ void device_nodes(const HostZGrid& h, lzq::ZNode* dst) {
     dst[k] = k < h.nz ? lzq::ZNode{h.g4[k], ldexp(h.omega[k], -lzq::kOmegaBias)} : lzq::ZNode{glast, 0.0};
 }
 
+// The whole image (lzq::zimage_doubles(nzp) doubles): the nodes, then their weights once more, packed
+// (lzq_exp2.h zimage_pack; the accumulate-only loops read them there, LZQ_ACC_FEED).
+void grid_image(const HostZGrid& h, double* dst) {
+  lzq::ZNode* nodes = reinterpret_cast<lzq::ZNode*>(dst);
+  device_nodes(h, nodes);
+  lzq::zimage_pack(nodes, padded_nodes(h.nz));
+}
+const int kDefaultImage = lzq::zimage_doubles(LZQ_NZ);  // the default grid's; its exp table follows
+
 int ensure_device(int* dev_out) {
   int dev = 0;
   LZQ_HIP(hipGetDevice(&dev));
@@ -434,14 +446,14 @@ int ensure_device(int* dev_out) {
   build_exp_table();
   static_assert(sizeof(lzq::ZNode) == 2 * sizeof(double), "ZNode layout");
   static_assert(LZQ_NZ % lzq::kKUnroll == 0, "the default grid needs no padding");
-  std::vector<lzq::ZNode> host(LZQ_NZ + lzq::kTabN / 2);
-  device_nodes(h, host.data());
-  memcpy(&host[LZQ_NZ], g_exp2tab, sizeof(g_exp2tab));
-  const size_t bytes = host.size() * sizeof(lzq::ZNode);
-  lzq::ZNode* d = nullptr;
+  std::vector<double> host(kDefaultImage + lzq::kTabN);
+  grid_image(h, host.data());
+  memcpy(&host[kDefaultImage], g_exp2tab, sizeof(g_exp2tab));
+  const size_t bytes = host.size() * sizeof(double);
+  void* d = nullptr;
   LZQ_HIP(hipMalloc(&d, bytes));
   LZQ_HIP(hipMemcpy(d, host.data(), bytes, hipMemcpyHostToDevice));
-  g_dev_tab[dev] = d;
+  g_dev_tab[dev] = static_cast<lzq::ZNode*>(d);
   return LZQ_OK;
 }
 
@@ -500,11 +512,12 @@ int zgrid_for(int32_t nz, double z_max, DevZGrid& g, int* dev_out, bool cont = f
   rc = build_ztable(nz, z_max, h);
   if (rc) return rc;
   const int32_t nzp = padded_nodes(nz);
-  std::vector<lzq::ZNode> host(nzp);
-  device_nodes(h, host.data());
-  lzq::ZNode* d = nullptr;
-  LZQ_HIP(hipMalloc(&d, host.size() * sizeof(lzq::ZNode)));
-  LZQ_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(lzq::ZNode), hipMemcpyHostToDevice));
+  std::vector<double> host(lzq::zimage_doubles(nzp));
+  grid_image(h, host.data());
+  void* dv = nullptr;
+  LZQ_HIP(hipMalloc(&dv, host.size() * sizeof(double)));
+  LZQ_HIP(hipMemcpy(dv, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice));
+  lzq::ZNode* d = static_cast<lzq::ZNode*>(dv);
   g_zgrids.push_back(ZGridEntry{dev, nz, zb, d, nzp, h.monotone});
   g.zt = d;
   g.nzp = nzp;

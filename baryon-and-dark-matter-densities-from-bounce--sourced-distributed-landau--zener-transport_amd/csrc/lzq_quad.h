@@ -21,7 +21,7 @@
 
 namespace lzq {
 
-// The five fast-path levels of the dense z-sum and y-loop.  Each is a switch only because a host test
+// The six fast-path levels of the dense z-sum and y-loop.  Each is a switch only because a host test
 // builds it with =0 and pins the result to the recorded machine code of the commit before it; the full
 // account of every level is DESIGN.md §4.1.  A level whose "needs" are not at their defaults is off.
 //
@@ -38,6 +38,9 @@ namespace lzq {
 //   LZQ_PASS_LEAN     0, 1     y, e^y and the weight stay live across the loops that      all four at their
 //                              have room; clamp-free exp_sc; interior y-nodes; the        defaults
 //                              dead/clamped mixed pass (zsum_uniform_lane)
+//   LZQ_ACC_FEED      0, 1     the accumulate-only loops (zsum_dead, zsum_held, single    all five at their
+//                              and grouped) read omega' from the image's packed array:    defaults
+//                              one 64-byte line per 8-node batch, not two
 #ifndef LZQ_ZERO_SEG
 #define LZQ_ZERO_SEG 1
 #endif
@@ -53,12 +56,17 @@ namespace lzq {
 #ifndef LZQ_PASS_LEAN
 #define LZQ_PASS_LEAN 1
 #endif
+#ifndef LZQ_ACC_FEED
+#define LZQ_ACC_FEED 1
+#endif
 static_assert(LZQ_GROUP_SEG == 0 || LZQ_GROUP_SEG == 2 || LZQ_GROUP_SEG == 4, "LZQ_GROUP_SEG is 0, 2 or 4");
 static_assert(LZQ_PASS_LEAN == 0 || LZQ_PASS_LEAN == 1, "LZQ_PASS_LEAN is 0 or 1");
+static_assert(LZQ_ACC_FEED == 0 || LZQ_ACC_FEED == 1, "LZQ_ACC_FEED is 0 or 1");
 constexpr int kFrozenSeg = (LZQ_ZERO_SEG != 0 && LZQ_DEAD_SEG != 0) ? LZQ_FROZEN_SEG : 0;
 constexpr int kGroupSeg = kFrozenSeg >= 1 ? LZQ_GROUP_SEG : 0;
 constexpr bool kLean = LZQ_ZERO_SEG == 1 && LZQ_DEAD_SEG == 1 && LZQ_FROZEN_SEG == 2 && LZQ_GROUP_SEG == 4 &&
                        LZQ_PASS_LEAN == 1;
+constexpr bool kAccFeed = kLean && LZQ_ACC_FEED == 1;
 
 constexpr int kNZ = LZQ_NZ;
 constexpr int kWaveSize = 64;
@@ -89,6 +97,16 @@ struct ZNode {
   double g4;     // fpy:156 gamma4(z_k), verbatim cancelling form
   double omega;  // z_k^2 e^{-z_k} * trapezoid weight of node k
 };
+
+// omega'_k of the accumulate-only loops.  FEED (LZQ_ACC_FEED): from the packed array behind the grid's nzp
+// nodes (zimage_omega, lzq_exp2.h) -- the node's own bits, one 64-byte line per batch -- else from the node
+// itself.  FEED is the dense, untruncated pass's and the A/V kernels'; the truncated passes and the table
+// mode keep reading the nodes, so the on-device controls of the dense kernels do not share the array.
+template <bool FEED>
+__device__ __forceinline__ double acc_omega(const ZNode* __restrict__ zt, int nzp, int k) {
+  if constexpr (FEED) return zimage_omega(zt, nzp)[k];
+  else return zt[k].omega;
+}
 
 // ---------------------------------------------------------------------------------------
 // per-point quadrature setup (wave-uniform values)
@@ -402,7 +420,9 @@ __device__ __forceinline__ double c2_scale() { return EXPV == kExpTable ? (doubl
 // tests/test_gpu_zsum_zero_segment.py, tests/test_gpu_zsum_dead_segment.py, tests/test_gpu_zsum_frozen.py).
 // Those accumulate-only nodes (42.8%) are bound by the feed of omega', not by their one instruction: where
 // consecutive passes are accumulate-only from node 0, yb_wave sweeps up to four of them through z together
-// (LZQ_GROUP_SEG, yb_group below; tests/test_zsum_group_host.py, tests/test_gpu_zsum_group.py).
+// (LZQ_GROUP_SEG, yb_group below; tests/test_zsum_group_host.py, tests/test_gpu_zsum_group.py), and all of
+// them, grouped or not, read omega' from the packed array of the grid's image, one line per 8-node batch
+// instead of two (LZQ_ACC_FEED, acc_omega; tests/test_zsum_feed_host.py, tests/test_gpu_zsum_feed.py).
 template <int YB, int EXPV, bool CLAMP = true>
 __device__ __forceinline__ void zsum(const ZNode* __restrict__ zt, const double* tab, const double (&c2)[YB],
                                      double (&F)[YB], int kend) {
@@ -546,9 +566,10 @@ __device__ __forceinline__ void zsum_uniform_lane(const ZNode* __restrict__ zt, 
 // are the same two numbers at each of them (seg_node_dead): they are formed once, and a node is F's
 // accumulate alone, F = fma(omega'_k, v0, F), on the operands zsum_uniform<YB, true> hands it, in node
 // order from F = 0.  No node is skipped.  v0 takes the loop's one pinned VGPR pair; omega' is the
-// instruction's scalar operand, and g4 is not read.
-template <int YB>
-__device__ __forceinline__ void zsum_dead(const ZNode* __restrict__ zt, double Ts, double (&F)[YB], int kend) {
+// instruction's scalar operand, and g4 is not read.  FEED (LZQ_ACC_FEED): omega' comes from the packed
+// array behind the grid's nzp nodes (acc_omega), the same bits out of one 64-byte line per batch.
+template <int YB, bool FEED = false>
+__device__ __forceinline__ void zsum_dead(const ZNode* __restrict__ zt, int nzp, double Ts, double (&F)[YB], int kend) {
 #pragma unroll
   for (int b = 0; b < YB; ++b) F[b] = 0.0;
   // (YB > 1: the chains start from the same 0 and add the same terms; opaque starts keep them YB
@@ -561,7 +582,7 @@ __device__ __forceinline__ void zsum_dead(const ZNode* __restrict__ zt, double T
   for (int k = 0; k < kend; k += kKUnroll) {
     double om[kKUnroll];
 #pragma unroll
-    for (int kk = 0; kk < kKUnroll; ++kk) om[kk] = zt[k + kk].omega;
+    for (int kk = 0; kk < kKUnroll; ++kk) om[kk] = acc_omega<FEED>(zt, nzp, k + kk);
 #pragma unroll
     for (int kk = 0; kk < kKUnroll; ++kk)
 #pragma unroll
@@ -573,10 +594,10 @@ __device__ __forceinline__ void zsum_dead(const ZNode* __restrict__ zt, double T
 // s = fma(c2, g, A) already has the value it has at the last executed node, so each lane's v is one
 // number on all of them (v[b]: seg_node_zero at that node, formed by the caller).  A node is F's
 // accumulate alone, F = fma(omega'_k, v, F), in node order, carrying on from kbeg: zsum_dead's loop
-// with a per-lane value, and these lanes are live, so F is kept.  No node is skipped.
-template <int YB>
-__device__ __forceinline__ void zsum_held(const ZNode* __restrict__ zt, const double (&v)[YB], double (&F)[YB], int kend,
-                                          int kbeg) {
+// with a per-lane value, and these lanes are live, so F is kept.  No node is skipped.  (FEED: as zsum_dead.)
+template <int YB, bool FEED = false>
+__device__ __forceinline__ void zsum_held(const ZNode* __restrict__ zt, int nzp, const double (&v)[YB], double (&F)[YB],
+                                          int kend, int kbeg) {
   if (kbeg == 0) {
 #pragma unroll
     for (int b = 0; b < YB; ++b) F[b] = 0.0;
@@ -584,7 +605,7 @@ __device__ __forceinline__ void zsum_held(const ZNode* __restrict__ zt, const do
   for (int k = kbeg; k < kend; k += kKUnroll) {
     double om[kKUnroll];
 #pragma unroll
-    for (int kk = 0; kk < kKUnroll; ++kk) om[kk] = zt[k + kk].omega;
+    for (int kk = 0; kk < kKUnroll; ++kk) om[kk] = acc_omega<FEED>(zt, nzp, k + kk);
 #pragma unroll
     for (int kk = 0; kk < kKUnroll; ++kk)
 #pragma unroll
@@ -669,6 +690,9 @@ __device__ __forceinline__ double shfl_xor_rederived(double v, int off) {
 // Returns whether the pass ran as F's accumulate alone from node 0 (all lanes dead, or a zero pass with
 // k3 = 0): what yb_wave's pass grouping (LZQ_GROUP_SEG) takes as its cue to try a group next.
 //
+// FEEDOK (LZQ_ACC_FEED): the accumulate-only loops of an untruncated pass may read the packed omega' array;
+// false for the table mode, which like the truncated pass stays on the nodes (the dense kernels' controls).
+//
 // after_general (LZQ_PASS_LEAN; yb_wave's): called at the end of the branches that ran the table-lookup
 // loop zsum<>, and of no other.  What the caller keeps in registers across the lean loops it re-forms
 // there, so that on the control-flow graph those values are dead through zsum<>, which has no room for
@@ -677,7 +701,7 @@ struct NoAfterGeneral {
   __device__ __forceinline__ void operator()() const {}
 };
 
-template <int YB, int EXPV, int NZ = 0, typename After = NoAfterGeneral>
+template <int YB, int EXPV, int NZ = 0, bool FEEDOK = true, typename After = NoAfterGeneral>
 __device__ __forceinline__ bool zsum_dispatch(const ZNode* __restrict__ zt, int nzp, const double* tab,
                                               const double (&c2)[YB], double (&F)[YB], int truncate = 0,
                                               const After& after_general = After()) {
@@ -736,7 +760,9 @@ __device__ __forceinline__ bool zsum_dispatch(const ZNode* __restrict__ zt, int 
 #pragma unroll
     for (int b = 0; b < YB; ++b) all_dead = all_dead && dead[b];
     if (LZQ_ZERO_SEG != 0 && LZQ_DEAD_SEG != 0 && __all(all_dead)) {
-      zsum_dead<YB>(zt, uniform(seg_entry(tab, zero_magic<(kFrozenSeg > 0)>(Mv))), F, kend);
+      const double Ts0 = uniform(seg_entry(tab, zero_magic<(kFrozenSeg > 0)>(Mv)));
+      if (kAccFeed && FEEDOK && !truncate) zsum_dead<YB, kAccFeed && FEEDOK>(zt, nz, Ts0, F, kend);
+      else zsum_dead<YB>(zt, nz, Ts0, F, kend);
       acc_only = true;
     } else if (__all(zero)) {
       const double Ts0 = uniform(seg_entry(tab, zero_magic<(kFrozenSeg > 0)>(Mv)));
@@ -760,7 +786,8 @@ __device__ __forceinline__ bool zsum_dispatch(const ZNode* __restrict__ zt, int 
           double v[YB];
 #pragma unroll
           for (int b = 0; b < YB; ++b) v[b] = seg_value_frozen_s(c2e[b], g_last, Av, Ts0);
-          zsum_held<YB>(zt, v, F, kend, k3);
+          if (kAccFeed && FEEDOK && !truncate) zsum_held<YB, kAccFeed && FEEDOK>(zt, nz, v, F, kend, k3);
+          else zsum_held<YB>(zt, nz, v, F, kend, k3);
         }
       } else {
         zsum_uniform<YB, LZQ_ZERO_SEG != 0>(zt, Ts0, c2e, F, kend, 0);
@@ -948,13 +975,13 @@ __device__ __forceinline__ int yb_group(Slot* slots, int w, const ZNode* __restr
         v[b] = seg_value_frozen_s(((cls >> (2 * b)) & kGrpDead) ? 0.0 : c2g[b], g_last, Av, Ts0);
     }
     if (G >= 4 && ran == 4) {
-      if (all_dead) zsum_dead<G>(zt, Ts0, F, nz);
-      else zsum_held<G>(zt, v, F, nz, 0);
+      if (all_dead) zsum_dead<G, kAccFeed>(zt, nz, Ts0, F, nz);
+      else zsum_held<G, kAccFeed>(zt, nz, v, F, nz, 0);
     } else {
       double F2[2];
       const double v2[2] = {v[0], v[1]};
-      if (all_dead) zsum_dead<2>(zt, Ts0, F2, nz);
-      else zsum_held<2>(zt, v2, F2, nz, 0);
+      if (all_dead) zsum_dead<2, kAccFeed>(zt, nz, Ts0, F2, nz);
+      else zsum_held<2, kAccFeed>(zt, nz, v2, F2, nz, 0);
 #pragma unroll
       for (int b = 0; b < G; ++b) F[b] = b < 2 ? F2[b] : 0.0;
     }
@@ -1062,7 +1089,7 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
       if constexpr (kLeanHere) {
         // y, e^y and the weight stay live through the lean loops; a pass that ran the table-lookup loop
         // re-forms them on its own branch (zsum_dispatch's after_general), as every pass did before
-        grp = zsum_dispatch<YB, EXPV, NZ>(zt, nzp, tab, c2, F, truncate, [&]() {
+        grp = zsum_dispatch<YB, EXPV, NZ, MODE == kYbDense>(zt, nzp, tab, c2, F, truncate, [&]() {
           int wa = w;
           asm volatile("" : "+s"(wa));
           const int la = lane_id();
@@ -1071,7 +1098,7 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
             y_triple<true>(slots[wa].s, base + b * kWaveSize + la, n, interior, yv[b], ey[b], wt[b]);
         });
       } else {
-        grp = zsum_dispatch<YB, EXPV, NZ>(zt, nzp, tab, c2, F, truncate);
+        grp = zsum_dispatch<YB, EXPV, NZ, MODE == kYbDense>(zt, nzp, tab, c2, F, truncate);
       }
       if constexpr (MODE == kYbTable) {
 #pragma unroll

@@ -37,6 +37,13 @@ ISA by tools/pass_valu.py (profiles/round12/pass_valu.json: both builds, per pat
 plan); together they predict the VALU per wave-node from the PMC of the build without them
 (profiles/round12/parent_pmc_summary.json).
 
+And the packed feed (LZQ_ACC_FEED), planned by tests/zsum_feed_host.cpp on the grid's device image as the
+library builds it: the nodes whose omega' comes from the packed array (the grouped sweeps, the whole
+accumulate-only passes outside a group, the held tails), and the 64-byte lines of the z table that one
+point's scalar loads touch before and after -- an 8-node batch is two lines of the interleaved nodes, one
+of the packed array; a group's sweep loads each batch once for all its chains.  No instruction count
+changes; what the array buys is feed time (profiles/round13).
+
     python tools/uniform_segment_share.py
 """
 import json
@@ -51,6 +58,7 @@ import test_zsum_dead_segment_host as H  # noqa: E402
 import test_zsum_frozen_host as HF        # noqa: E402
 import test_zsum_group_host as HG         # noqa: E402
 import test_zsum_mixed_host as HM         # noqa: E402
+import test_zsum_feed_host as HFD         # noqa: E402
 import zsum_ref as Z                      # noqa: E402
 
 
@@ -141,13 +149,32 @@ def lean_counts(g, c2):
     return {"pass_lean": out}
 
 
+def feed_counts(g, c2_nodes):
+    """The nodes of LZQ_ACC_FEED on the point's y-nodes c2_nodes (unpadded), and the z-table lines touched."""
+    _, _, _, plan, _, fed = HFD.run(HFD.load_lib(), g, c2_nodes, 1)
+    size, path, first, k3 = plan[:, 0], plan[:, 1], plan[:, 2], plan[:, 3]
+    nodes = int(len(plan)) * g.nz
+    sweeps = int((size == 1).sum() + ((size > 1) & (first == 1)).sum())       # one pass over z each
+    fed_batches = int(fed[size == 1].sum() + fed[(size > 1) & (first == 1)].sum()) // 8
+    before = 2 * sweeps * (g.nz // 8)
+    tails = (size == 1) & (path == HFD.ZERO) & (k3 > 0) & (fed > 0)
+    return {"acc_feed": {
+        "nodes_fed": int(fed.sum()), "fed_share": float(fed.sum()) / nodes,
+        "nodes_fed_in_groups": int(fed[size > 1].sum()),
+        "nodes_fed_whole_single_passes": int(fed[(size == 1) & (fed == g.nz)].sum()),
+        "nodes_fed_held_tails": int(fed[tails].sum()), "held_tails": int(tails.sum()),
+        "z_sweeps_per_point": sweeps, "batches_fed": fed_batches,
+        "z_table_lines_per_point_before": before, "z_table_lines_per_point_after": before - fed_batches,
+        "lines_saved_share": fed_batches / before}}
+
+
 def main():
     B, Tp, I_p = 100.0, 100.0, 0.34                  # yields_config_equal_mass.json (C2's base)
     y_of = lambda T: 0.5 * B * ((Tp / T) ** 2 - 1.0)
     ys = np.linspace(max(y_of(5.0 * Tp), -80.0), min(y_of(1e-3 * Tp), 50.0), 8000)
     g = Z.grid(1200, 30.0)
     c2 = ((-(I_p / 6.0) * np.exp(np.clip(ys, -50.0, 50.0))) * Z.LOG2E) * 8192.0
-    grouped = group_counts(g, c2)
+    grouped = {**group_counts(g, c2), **feed_counts(g, c2)}
     c2 = np.concatenate([c2, np.full(-len(c2) % 64, c2[-1])])      # tail lanes recompute the last node
     L = H.load_lib()
     _, _, plan = H.run(L, g, c2, H.DEADSEG, 0)
