@@ -155,9 +155,6 @@ __global__ __launch_bounds__(kBlock, LZQ_MIN_WAVES) void grid_ztable_kernel(lzq_
   ztable_wave<EXPV>(slots, w, lane, qs, epilogue_pre(pt, P), zt, nzp, zk, tab, truncate, Fw + t * tstride);
 }
 
-#ifndef LZQ_REUSE_MIN_WAVES
-#define LZQ_REUSE_MIN_WAVES 8  // 8 waves/SIMD (SGPRs capped, a few spilled to VGPR lanes): +12% over 7 (tools/ablate_builds.py ... reuse)
-#endif
 __global__ __launch_bounds__(kBlock, LZQ_REUSE_MIN_WAVES) void grid_reuse_kernel(lzq_point base, GridSpec grid, int64_t start,
                                                            int64_t count, int32_t n_y,
                                                            const double* __restrict__ Pov, ZKey zk,

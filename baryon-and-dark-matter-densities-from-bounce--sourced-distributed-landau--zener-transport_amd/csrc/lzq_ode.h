@@ -16,13 +16,42 @@
 #include "lzq_internal.h"
 #include "lzq_physics.h"
 
-namespace lzq {
-
-
-// ode_integrate_kernel: minimum waves per SIMD (its VGPR cap = 512 / this)
+// ---------------------------------------------------------------------------------------
+// Build parameters of the ODE fallback (numeric; every settled on/off choice is plain code).
+//
+// | name               | default | what it sets                                              | measured                                |
+// |--------------------|---------|-----------------------------------------------------------|-----------------------------------------|
+// | LZQ_ODE_MIN_WAVES  | 2       | ode_integrate_kernel: waves/SIMD floor (VGPR cap 512 / n)  | profiles/round2/ablate_ode_waves.json   |
+// | LZQ_RIC_MIN_WAVES  | 4       | ode_riccati_kernel: waves/SIMD floor (VGPR cap 512 / n)    | round 5, DESIGN §4.3                    |
+// | LZQ_ODE_MIN_GROUP  | 8       | smallest cooperative segment, in lanes (64: whole waves)   | profiles/round2/ablate_ode_coop.json    |
+// | LZQ_ODE_ROWS_BLOCK | 256     | row-table waves stage 2x this many rows per block          | tools/time_ode_rows.py, DESIGN §4.3     |
+// | LZQ_ODE_ROWS_COPY  | 4       | row staging: loads in flight per lane                      | tools/time_ode_rows.py, DESIGN §4.3     |
+// | LZQ_ODE_PRED_BLOCK | 64      | steps per predictor block (pred_step below)                | DESIGN §4.3 (time-parallel integration) |
+//
+// LZQ_ODE_ROWS_COPY divides LZQ_ODE_ROWS_BLOCK / 64; LZQ_ODE_PRED_BLOCK is a power of two.
+// lzq_ode.hip adds LZQ_RIC_TAB_MIN_WAVES; LZQ_ODE_COOP_DEBUG and LZQ_ODE_TP_DEBUG are debug builds.
+// ---------------------------------------------------------------------------------------
 #ifndef LZQ_ODE_MIN_WAVES
 #define LZQ_ODE_MIN_WAVES 2
 #endif
+#ifndef LZQ_RIC_MIN_WAVES
+#define LZQ_RIC_MIN_WAVES 4
+#endif
+#ifndef LZQ_ODE_MIN_GROUP
+#define LZQ_ODE_MIN_GROUP 8
+#endif
+#ifndef LZQ_ODE_ROWS_BLOCK
+#define LZQ_ODE_ROWS_BLOCK 256
+#endif
+#ifndef LZQ_ODE_ROWS_COPY
+#define LZQ_ODE_ROWS_COPY 4
+#endif
+#ifndef LZQ_ODE_PRED_BLOCK
+#define LZQ_ODE_PRED_BLOCK 64
+#endif
+
+namespace lzq {
+
 constexpr int kOdeBlock = 256;
 constexpr double kInvMplGeV = 1.0 / kMplGeV;
 
@@ -78,22 +107,6 @@ __device__ __forceinline__ OdePoint ode_point(const lzq_point& pt, const lzq_ode
   return o;
 }
 
-#ifndef LZQ_ODE_MIN_GROUP
-#define LZQ_ODE_MIN_GROUP 8  // smallest cooperative segment (64: whole wavefronts only, round 2)
-#endif
-#ifndef LZQ_ODE_PREDICT
-#define LZQ_ODE_PREDICT 1  // Radau5 collocation predictor for the Riccati Newton iteration
-#endif
-#ifndef LZQ_ODE_FASTMATH
-#define LZQ_ODE_FASTMATH 1  // 0: IEEE division and ROCm exp in the stage function (tools/ablate_ode.py);
-#endif
-#ifndef LZQ_ODE_COOP
-#define LZQ_ODE_COOP 1  // cooperative stage tables for group-uniform wavefronts (ode_integrate_kernel)
-#endif
-#ifndef LZQ_ODE_FMA
-#define LZQ_ODE_FMA LZQ_ODE_FASTMATH  // fused multiply-adds in the spline, the window exponent, Newton's f
-#endif
-
 // fpy:214-218 A_over_V_T: min(max(T, T_lo), T_hi), then the PPoly of scipy (_ppoly.pyx:
 // interval k with T_k <= T < T_{k+1}, T == T_hi in the last one; c3 + c2 s + c1 s^2 + c0 s^3
 // accumulated in that order, powers by repeated multiplication).  nt: the table's knot count
@@ -117,14 +130,7 @@ __device__ __forceinline__ SplineLoc spline_loc(const OdePoint& o, double T, int
 
 // the cubic of one interval, c = (c0, c1, c2, c3) of the PPoly row
 __device__ __forceinline__ double spline_cubic(const double (&c)[4], double s) {
-  if (LZQ_ODE_FMA) return __builtin_fma(__builtin_fma(__builtin_fma(c[0], s, c[1]), s, c[2]), s, c[3]);  // Horner
-  double z = s, res = c[3];
-  res = res + c[2] * z;
-  z = z * s;
-  res = res + c[1] * z;
-  z = z * s;
-  res = res + c[0] * z;
-  return res;
+  return __builtin_fma(__builtin_fma(__builtin_fma(c[0], s, c[1]), s, c[2]), s, c[3]);  // Horner
 }
 
 __device__ __forceinline__ double spline_at(const double* __restrict__ w, double s, int k) {
@@ -143,7 +149,6 @@ __device__ __forceinline__ double spline_eval(const OdePoint& o, const double* _
 // 1/x for a positive normal x: v_rcp_f64 + two Newton steps (5 VALU; <= 1 ulp from the
 // correctly rounded quotient, which costs ~10).
 __device__ __forceinline__ double rcp_pos(double x) {
-  if (!LZQ_ODE_FASTMATH) return 1.0 / x;
   double r = __builtin_amdgcn_rcp(x);
   double e = __builtin_fma(-x, r, 1.0);
   r = __builtin_fma(r, e, r);
@@ -155,7 +160,6 @@ __device__ __forceinline__ double rcp_pos(double x) {
 // reduced argument; the one rounding of v log2 e costs |v| 2^-53 relative, < 1e-13 for
 // |v| < 700, where the factor is still > 1e-304).  ~16 VALU against ~22 for ROCm's exp.
 __device__ __forceinline__ double exp_nonpos(double v) {
-  if (!LZQ_ODE_FASTMATH) return exp(v);
   return exp2_nonpos(v * kLog2E, 1.0);
 }
 
@@ -198,7 +202,7 @@ __device__ __forceinline__ StageBase ode_stage_base(const OdePoint& o, const dou
   const double T3 = (T * T) * T;
   const double s = pymax(o.s0 * T3, 1e-300);                  // fpy:274 via fpy:88
   const double qT = o.Tp * iT;                                // fpy:275 y_of_T (fpy:126-128)
-  const double y = 0.5 * o.B * (LZQ_ODE_FMA ? __builtin_fma(qT, qT, -1.0) : qT * qT - 1.0);
+  const double y = 0.5 * o.B * __builtin_fma(qT, qT, -1.0);
   const double q = y * o.inv_sig;
   const double window = exp_nonpos(-0.5 * (q * q));           // fpy:276
   double n_eq, vbar;                                          // fpy:90-120
@@ -359,45 +363,10 @@ __device__ __forceinline__ bool block_guess(const Radau& R, double h, const OdeS
   return ok;
 }
 
-// x = M^-1 b for the 3x3 stage matrices M = I + h A diag(d) (partial pivoting; branch-free
-// selects, so the lanes of a wave stay converged).
-__device__ __forceinline__ void solve3(double M[3][3], double b[3]) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-#pragma unroll
-    for (int r = c + 1; r < 3; ++r) {
-      const bool sw = fabs(M[r][c]) > fabs(M[c][c]);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const double t = M[c][k];
-        M[c][k] = sw ? M[r][k] : t;
-        M[r][k] = sw ? t : M[r][k];
-      }
-      const double t = b[c];
-      b[c] = sw ? b[r] : t;
-      b[r] = sw ? t : b[r];
-    }
-#pragma unroll
-    for (int r = c + 1; r < 3; ++r) {
-      const double f = M[r][c] / M[c][c];
-#pragma unroll
-      for (int k = c; k < 3; ++k) M[r][k] = M[r][k] - f * M[c][k];
-      b[r] = b[r] - f * b[c];
-    }
-  }
-#pragma unroll
-  for (int c = 2; c >= 0; --c) {
-    double acc = b[c];
-#pragma unroll
-    for (int k = c + 1; k < 3; ++k) acc = acc - M[c][k] * b[k];
-    b[c] = acc / M[c][c];
-  }
-}
-
 // z[2] of M z = b by Cramer's rule (one division): the Y_B stage system needs only the last
 // stage.  M = I + h A diag(beta), beta >= 0, is well conditioned for every h (A of Radau IIA
-// has eigenvalues in the right half plane), so the cofactor form loses nothing against the
-// pivoted elimination of solve3 (tests/test_gpu_ode.py: oracle at 1e-11).
+// has eigenvalues in the right half plane), so the cofactor form loses nothing against
+// pivoted elimination (tests/test_gpu_ode.py: oracle at 1e-11).
 __device__ __forceinline__ double solve3_last(const double (&M)[3][3], const double (&b)[3]) {
   const double c0 = M[1][0] * M[2][1] - M[1][1] * M[2][0];
   const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) -
@@ -423,59 +392,7 @@ __device__ __forceinline__ RadauH radau_h(const Radau& R, double h) {
   return r;
 }
 
-// x = M^-1 b by the adjugate (one division for all three components), for the Newton stage
-// systems M = I - hA diag(jf) of the Riccati equation: well conditioned like the Y_B system
-// (jf = -2 lam Z <= 0 near the solution), so the cofactor form loses nothing against pivoted
-// elimination (tests/test_gpu_ode.py: oracle at 1e-11, stiff cases at 1e-10 of converged).
-#ifndef LZQ_ODE_ADJFMA
-#define LZQ_ODE_ADJFMA 1  // the adjugate, determinant and products as explicit fmas (the file builds with -ffp-contract=off)
-#endif
-struct Adj3 {
-  double a[3][3];  // adjugate of M
-  double id;       // 1 / det M
-};
-__device__ __forceinline__ Adj3 adj3(const double (&M)[3][3]) {
-  Adj3 r;
-  if (LZQ_ODE_ADJFMA) {
-#define FMA __builtin_fma
-    r.a[0][0] = FMA(M[1][1], M[2][2], -(M[1][2] * M[2][1]));
-    r.a[0][1] = FMA(M[0][2], M[2][1], -(M[0][1] * M[2][2]));
-    r.a[0][2] = FMA(M[0][1], M[1][2], -(M[0][2] * M[1][1]));
-    r.a[1][0] = FMA(M[1][2], M[2][0], -(M[1][0] * M[2][2]));
-    r.a[1][1] = FMA(M[0][0], M[2][2], -(M[0][2] * M[2][0]));
-    r.a[1][2] = FMA(M[0][2], M[1][0], -(M[0][0] * M[1][2]));
-    r.a[2][0] = FMA(M[1][0], M[2][1], -(M[1][1] * M[2][0]));
-    r.a[2][1] = FMA(M[0][1], M[2][0], -(M[0][0] * M[2][1]));
-    r.a[2][2] = FMA(M[0][0], M[1][1], -(M[0][1] * M[1][0]));
-    r.id = 1.0 / FMA(M[0][0], r.a[0][0], FMA(M[0][1], r.a[1][0], M[0][2] * r.a[2][0]));
-#undef FMA
-  } else {
-    r.a[0][0] = M[1][1] * M[2][2] - M[1][2] * M[2][1];
-    r.a[0][1] = M[0][2] * M[2][1] - M[0][1] * M[2][2];
-    r.a[0][2] = M[0][1] * M[1][2] - M[0][2] * M[1][1];
-    r.a[1][0] = M[1][2] * M[2][0] - M[1][0] * M[2][2];
-    r.a[1][1] = M[0][0] * M[2][2] - M[0][2] * M[2][0];
-    r.a[1][2] = M[0][2] * M[1][0] - M[0][0] * M[1][2];
-    r.a[2][0] = M[1][0] * M[2][1] - M[1][1] * M[2][0];
-    r.a[2][1] = M[0][1] * M[2][0] - M[0][0] * M[2][1];
-    r.a[2][2] = M[0][0] * M[1][1] - M[0][1] * M[1][0];
-    r.id = 1.0 / (M[0][0] * r.a[0][0] + M[0][1] * r.a[1][0] + M[0][2] * r.a[2][0]);
-  }
-  return r;
-}
-__device__ __forceinline__ void adj3_apply(const Adj3& A, double (&b)[3]) {
-  double x[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-    x[i] = LZQ_ODE_ADJFMA ? __builtin_fma(A.a[i][0], b[0], __builtin_fma(A.a[i][1], b[1], A.a[i][2] * b[2])) * A.id
-                          : (A.a[i][0] * b[0] + A.a[i][1] * b[1] + A.a[i][2] * b[2]) * A.id;
-  b[0] = x[0];
-  b[1] = x[1];
-  b[2] = x[2];
-}
-__device__ __forceinline__ void solve3_adj(const double (&M)[3][3], double (&b)[3]) { adj3_apply(adj3(M), b); }
-
-// Y_B's Radau step as an affine map (LZQ_ODE_YBREC): the stage system (I + hA diag(beta)) Z =
+// Y_B's Radau step as an affine map: the stage system (I + hA diag(beta)) Z =
 // Y_B 1 + hA alpha, alpha_j = P flux a_j, gives by Cramer's rule Z_3 = c Y_B + P flux d with
 // c = (w0 + w1 + w2)/det and d = sum_j (sum_i w_i hA_ij) a_j / det, w_i the cofactors of the last
 // column's numerator (solve3_last's).  c and d depend on the point only through Gamma_wash (beta)
@@ -522,9 +439,6 @@ __device__ __forceinline__ YbRec yb_rec(const RadauH& hA, const OdeStage (&st)[3
   return yb_rec(hA, beta, a);
 }
 
-// One Radau step for both equations (hA = h * A of the step); false when the Y_chi Newton
-// iteration fails.  The stage sums are explicit fmas (hA_ij * f_j + acc); only the last stage
-// of each equation is the step's result, so the linear cases form only what they need.
 // Newton starting values for the next step's Riccati stages: the previous step's collocation
 // polynomial (through Y at its start and its three stage values, nodes 0, c1, c2, 1) evaluated
 // at 1 + c_j (Lagrange weights, mpmath): the standard Radau5 predictor.
@@ -534,7 +448,7 @@ static __constant__ double kRadauPred[3][4] = {
     {-0x1.9000000000000p+4, 0x1.51cdd7dde1522p+5, -0x1.07232d3336a77p+5, 0x1.0aaaaaaaaaaabp+4}};
 
 // A^-1 of the Radau IIA matrix (mpmath, rounded once) and the products of its off-diagonal pairs
-// that the transformed Newton system's adjugate needs (LZQ_ODE_TNEWTON):
+// that the transformed Newton system's adjugate needs:
 // [a12 a21, a02 a21, a01 a12, a12 a20, a02 a20, a02 a10, a10 a21, a01 a20, a01 a10].
 static __constant__ double kRadauAinv[3][3] = {
     {0x1.9cc470a049097p+1, 0x1.2af7915ab4027p+0, -0x1.034624ce046cap-2},
@@ -560,71 +474,18 @@ __device__ __forceinline__ double fma_neg_s(double k, double a, double p) {
   return r;
 }
 
-#ifndef LZQ_ODE_TNEWTON
-#define LZQ_ODE_TNEWTON 1  // the Riccati Newton iteration in the transformed form (constant off-diagonals)
-#endif
-#ifndef LZQ_ODE_NEWTON_RCP
-#define LZQ_ODE_NEWTON_RCP 1  // the Newton solve's 1/det by rcp_pos (5 VALU) instead of the IEEE quotient (~14)
-#endif
-
-// Zs: in, Newton starting stages when `guess` (else Ychi for all three); out, the converged
-// stages (the next predictor's data).  A predicted start that does not converge is retried
-// from Ychi, so the predictor can only save iterations, never lose a step.
-#ifndef LZQ_ODE_PEEL
-#define LZQ_ODE_PEEL 1  // the first two Newton iterations (and the Y_B solve) as one straight-line block
-#endif
-#ifndef LZQ_ODE_NEWTON2
-#define LZQ_ODE_NEWTON2 1  // the peeled pair of Newton iterations always both applied (no iterate selects)
-#endif
-#ifndef LZQ_ODE_SIMPLIFIED
-#define LZQ_ODE_SIMPLIFIED 1  // the peeled pair's second iteration reuses the first one's adjugate and 1/det
-#endif
-#ifndef LZQ_ODE_KD
-#define LZQ_ODE_KD 1  // the step index as a carried exact double (no 64-bit integer conversion per step)
-#endif
-#ifndef LZQ_ODE_NOSPLITVAR
-#define LZQ_ODE_NOSPLITVAR 1  // waves with no split step in the launch run an integrator variant without the split paths
-#endif
-#ifndef LZQ_ODE_LINFAST
-#define LZQ_ODE_LINFAST 1  // one fma per regular step on linear cooperative waves (sigma_v = 0, no depletion)
-#endif
-#ifndef LZQ_ODE_YBREC
-#define LZQ_ODE_YBREC 1  // Y_B by its affine step map (yb_rec), shared per cooperative segment
-#endif
-#ifndef LZQ_ODE_RICVAR
-#define LZQ_ODE_RICVAR 1  // whole-wave cooperative split-free waves run ode_riccati_kernel (compact rows, uniform constants)
-#endif
-#ifndef LZQ_ODE_RICTAB
-#define LZQ_ODE_RICTAB 1  // table-varying whole waves too, through ode_riccati_kernel<., true> (round 6; RicRowT)
-#endif
-#ifndef LZQ_ODE_RICSEG
-#define LZQ_ODE_RICSEG 1  // split-free waves of uniform 32/16/8-lane segments through ode_riccati_kernel<0, false, true>
-#endif
-#ifndef LZQ_ODE_ROWS
-#define LZQ_ODE_ROWS 1  // linear waves read their run's shared row table when given one (lzq_ode_integrate_rows)
-#endif
-#ifndef LZQ_ODE_ROWS_ASYNC
-#define LZQ_ODE_ROWS_ASYNC 0  // 1: row-table waves fetch the next block into LDS (global_load_lds) while a block steps (measured slower)
-#endif
-#ifndef LZQ_ODE_ROWS_COPY
-#define LZQ_ODE_ROWS_COPY 4  // row staging: loads in flight per lane (a divisor of LZQ_ODE_ROWS_BLOCK / 64)
-#endif
-#ifndef LZQ_ODE_ROWS_BLOCK
-#define LZQ_ODE_ROWS_BLOCK 256   // row-table waves stage 2x this many rows per block (LZQ_ODE_ROWS_ASYNC: two buffers of it)
-#endif
-#ifndef LZQ_ODE_PRED_BLOCK
 // The Radau5 predictor is not used on steps k = 0 (mod LZQ_ODE_PRED_BLOCK): every block of that
 // many steps starts its Newton iteration from Y_chi, so a block's end state is a function of its
 // start (Y_chi, Y_B) alone -- what lzq_ode_integrate_tp's exact stitching needs.  Every integrator
-// applies the rule on the absolute step index, so all modes stay bit-identical.  (A power of two.)
-#define LZQ_ODE_PRED_BLOCK 64
-#endif
-
+// applies the rule on the absolute step index, so all modes stay bit-identical.
 __device__ __forceinline__ bool pred_step(int64_t k) { return (k & (LZQ_ODE_PRED_BLOCK - 1)) != 0; }
-#ifndef LZQ_RIC_MIN_WAVES
-#define LZQ_RIC_MIN_WAVES 4  // ode_riccati_kernel: minimum waves per SIMD (its VGPR cap = 512 / this)
-#endif
 
+// One Radau step for both equations (hA = h * A of the step); false when the Y_chi Newton
+// iteration fails.  The stage sums are explicit fmas (hA_ij * f_j + acc); only the last stage
+// of each equation is the step's result, so the linear cases form only what they need.
+// Zs: in, Newton starting stages when `guess` (else Ychi for all three); out, the converged
+// stages (the next predictor's data).  A predicted start that does not converge is retried
+// from Ychi, so the predictor can only save iterations, never lose a step.
 template <bool kWithYB = true>
 __device__ __forceinline__ bool radau_step(const RadauH& hA, const OdeStage (&st)[3], double& Ychi, double& YB,
                                            double (&Zs)[3], bool guess) {
@@ -646,14 +507,15 @@ __device__ __forceinline__ bool radau_step(const RadauH& hA, const OdeStage (&st
   // Y_chi: Z_i = Y + h sum_j a_ij f_j(Z_j), f_j(Z) = -lam_j (Z^2 - E2_j) - S_j; one Newton
   // iteration on Z, true when its correction is below 1e-15 of the stages
   const double Y0 = Ychi;
-#if LZQ_ODE_TNEWTON && LZQ_ODE_FASTMATH
   // Transformed Newton system: (I - hA diag(jf)) g = -(Z - Y0 - hA f) times h (hA)^-1 is
   //   (A^-1 - diag(h jf)) g = h f - A^-1 (Z - Y0),
   // whose matrix keeps A^-1's constant off-diagonals (kRadauAinv) and changes only on the diagonal,
   // A^-1_jj + 2 h lam_j Z_j: its adjugate is one fma per entry against constant products
   // (kRadauAinvP), and the h-scaled stage data h lam_j, 2 h lam_j, h S_j are formed once per step.
   // Same fixed point (the stage equations), ~20 FP64 instructions fewer per iteration than
-  // forming I - hA diag(jf) and its full adjugate.
+  // forming I - hA diag(jf) and its full adjugate.  The system is well conditioned
+  // like Y_B's (jf = -2 lam Z <= 0 near the solution), so the cofactor form loses nothing against
+  // pivoted elimination (tests/test_gpu_ode.py: oracle at 1e-11, stiff cases at 1e-10 of converged).
   double hl[3], hl2[3], hS[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
@@ -661,7 +523,7 @@ __device__ __forceinline__ bool radau_step(const RadauH& hA, const OdeStage (&st
     hl2[j] = 2.0 * hl[j];
     hS[j] = hA.h * st[j].S;
   }
-  // the iteration matrix's adjugate and 1/det, kept for a simplified iteration (LZQ_ODE_SIMPLIFIED)
+  // the iteration matrix's adjugate and 1/det, kept for a simplified iteration
   struct NewtonJ {
     double b[3][3], id;
   };
@@ -687,7 +549,7 @@ __device__ __forceinline__ bool radau_step(const RadauH& hA, const OdeStage (&st
       // 1/det only scales the correction: a reciprocal within 1 ulp leaves the fixed point (the
       // stage equations) as it is and changes the iterates by rounding
       const double den = FMA(k[0], J.b[0][0], FMA(kRadauAinv[0][1], J.b[1][0], kRadauAinv[0][2] * J.b[2][0]));
-      J.id = LZQ_ODE_NEWTON_RCP ? rcp_pos(den) : 1.0 / den;
+      J.id = rcp_pos(den);
     }
     double g[3];
 #pragma unroll
@@ -707,41 +569,6 @@ __device__ __forceinline__ bool radau_step(const RadauH& hA, const OdeStage (&st
   NewtonJ J;
   bool near = false;
   auto newton = [&](double (&Z)[3]) { return newton_j(Z, J, false, near); };
-#else
-  auto newton = [&](double (&Z)[3]) {
-    double M[3][3], g[3];
-    double f[3], jf[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      f[j] = LZQ_ODE_FMA ? __builtin_fma(-st[j].lam, __builtin_fma(Z[j], Z[j], -st[j].E2), -st[j].S)
-                         : -st[j].lam * (Z[j] * Z[j] - st[j].E2) - st[j].S;
-      jf[j] = -st[j].lam * (2.0 * Z[j]);
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      double acc = Z[i] - Y0;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        acc = __builtin_fma(-hA.a[i][j], f[j], acc);
-        M[i][j] = __builtin_fma(-hA.a[i][j], jf[j], i == j ? 1.0 : 0.0);
-      }
-      g[i] = -acc;
-    }
-#if LZQ_ODE_FASTMATH
-    solve3_adj(M, g);
-#else
-    solve3(M, g);
-#endif
-    double dmax = 0.0, zmax = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      Z[i] = Z[i] + g[i];
-      dmax = fmax(dmax, fabs(g[i]));
-      zmax = fmax(zmax, fabs(Z[i]));
-    }
-    return !(dmax > 1e-15 * zmax);
-  };
-#endif
   auto accept = [&](const double (&Z)[3]) {
     Zs[0] = Z[0];
     Zs[1] = Z[1];
@@ -760,17 +587,13 @@ __device__ __forceinline__ bool radau_step(const RadauH& hA, const OdeStage (&st
   for (int attempt = guess ? 0 : 1; attempt < 2; ++attempt) {
     double Z[3] = {attempt == 0 ? Zs[0] : Y0, attempt == 0 ? Zs[1] : Y0, attempt == 0 ? Zs[2] : Y0};
     int it = 0;
-#if LZQ_ODE_PEEL
     if (attempt == (guess ? 0 : 1)) {
       // the first two iterations (and Y_B's independent solve) in one basic block, so the
-      // scheduler interleaves their dependent chains; the second is applied only if the first
-      // did not converge -- the same iterates as the loop below, bit for bit
+      // scheduler interleaves their dependent chains.  Both iterations always apply: a step that
+      // converged at the first takes the second's (below 1e-15 relative) correction too, so no
+      // selects between the two iterates are needed
       if (kWithYB) YB = yb_step();
-#if LZQ_ODE_NEWTON2
-      // both iterations always apply: a step that converged at the first takes the second's
-      // (below 1e-15 relative) correction too, so no selects between the two iterates are needed
       const bool c1 = newton(Z);
-#if LZQ_ODE_SIMPLIFIED && LZQ_ODE_TNEWTON && LZQ_ODE_FASTMATH
       // Once the first correction is below 1e-3 of the stages (the predicted start, almost every
       // step), the second iteration reuses the first one's matrix (simplified Newton): its
       // correction is then the first one's residual error to first order either way, so the
@@ -781,37 +604,12 @@ __device__ __forceinline__ bool radau_step(const RadauH& hA, const OdeStage (&st
       // depend on its wavefront.
       const bool reuse = near;
       const bool c2 = newton_j(Z, J, reuse, near);
-#else
-      const bool c2 = newton(Z);
-#endif
       if (c1 || c2) {
         accept(Z);
         return true;
       }
-#else
-      double Z2[3];
-      const bool c1 = newton(Z);
-      Z2[0] = Z[0];
-      Z2[1] = Z[1];
-      Z2[2] = Z[2];
-      const bool c2 = newton(Z2);
-      if (c1) {
-        accept(Z);
-        return true;
-      }
-      if (c2) {
-        accept(Z2);
-        return true;
-      }
-      Z[0] = Z2[0];
-      Z[1] = Z2[1];
-      Z[2] = Z2[2];
-#endif
       it = 2;
     }
-#else
-    if (kWithYB && attempt == (guess ? 0 : 1)) YB = yb_step();
-#endif
     for (; it < 40; ++it) {
       if (newton(Z)) {
         accept(Z);

@@ -18,6 +18,45 @@
 // lzq_ode_tp.hip (the time-parallel integration of a few points).
 #include "lzq_ode.h"
 
+// Build parameters of this file, beside lzq_ode.h's table:
+//
+// | name                  | default | what it sets                                                     | measured                |
+// |-----------------------|---------|------------------------------------------------------------------|-------------------------|
+// | LZQ_RIC_TAB_MIN_WAVES | 3       | ode_riccati_kernel<., kTab or kSeg>: waves/SIMD floor; its rows   | round 6, DESIGN §4.3    |
+// |                       |         | take 38 KB of LDS per 4-wave block, 3 blocks per CU               |                         |
+// | LZQ_QUAD_MIN_WAVES    | 3       | ode_quad_kernel: waves/SIMD floor                                 | tools/bench_ode.py      |
+// | LZQ_QUAD_UNROLL       | 1       | ode_quad_kernel: unroll of the 8 Gauss points of a sub-interval   | tools/bench_ode.py      |
+//
+// Two settled switches stay, because folding them changes the machine code of this file's kernels
+// (every other settled switch was folded with all code objects byte-equal):
+//
+// | LZQ_ODE_RICTAB        | 1 (0)   | table-varying whole waves through ode_riccati_kernel<., true>.     | round 6                 |
+// |                       |         | Without the `!tab_vary ||` test in ode_integrate_kernel's exit the |                         |
+// |                       |         | compiler lays out ode_integrate_kernel<false, false, .> differently |                        |
+// | LZQ_RIC_IP            | 2 (0,1) | ode_riccati_kernel's steps through ric_step_ip; 2: have / Yp        | round 6                 |
+// |                       |         | outside the joins.  The ric_step loop behind it (0) names           |                         |
+// |                       |         | kRadauPred, and where a table is first named decides its place in   |                         |
+// |                       |         | .rodata: without the loop all 13 ode_integrate and ode_riccati      |                         |
+// |                       |         | kernels come out different                                          |                         |
+//
+// LZQ_ODE_COOP_DEBUG (unset) builds ode_integrate_kernel to report each point's cooperative
+// segment width in P_used (tools/dbg_ode_coop.py).
+#ifndef LZQ_RIC_TAB_MIN_WAVES
+#define LZQ_RIC_TAB_MIN_WAVES 3
+#endif
+#ifndef LZQ_QUAD_MIN_WAVES
+#define LZQ_QUAD_MIN_WAVES 3
+#endif
+#ifndef LZQ_QUAD_UNROLL
+#define LZQ_QUAD_UNROLL 1
+#endif
+#ifndef LZQ_ODE_RICTAB
+#define LZQ_ODE_RICTAB 1
+#endif
+#ifndef LZQ_RIC_IP
+#define LZQ_RIC_IP 2
+#endif
+
 namespace lzq {
 int g_ode_coop = 1;          // lzq_tune(LZQ_TUNE_ODE_COOP)
 int g_ode_launch_log2 = 24;  // lzq_tune(LZQ_TUNE_ODE_LAUNCH_STEPS): <= 2^24 Radau steps per launch
@@ -269,9 +308,6 @@ __global__ __launch_bounds__(64 * kSplWaves) void ode_spline_wave_kernel(const l
 // kLin: the variant for linear cooperative waves (see lin_wave below); every launch runs both
 // variants, each stepping only its own wavefronts (the other variant's return at once), so the
 // linear waves' tight loop does not share a register allocation with the Riccati Newton path.
-#ifndef LZQ_ODE_GEN_RICSTEP
-#define LZQ_ODE_GEN_RICSTEP 1  // the general variant's regular Riccati steps through ric_step (round 6)
-#endif
 template <bool kDep>
 __device__ bool ric_step(double h, const double (&hA2)[3], const double (&lam)[3], const double (&E2)[3],
                          const double (&S)[3], const double (&pv)[6], double& Ychi, double (&Zs)[3], bool guess);
@@ -303,8 +339,8 @@ __global__ __launch_bounds__(kOdeBlock, LZQ_ODE_MIN_WAVES) void ode_integrate_ke
   __shared__ StageBase s_base[kOdeBlock / 64][64][3];  // cooperative mode
   // shared Y_B step maps, (c, d) and the cofactor weights in separate arrays: the linear waves'
   // tight loop streams 16-B (c, d) rows
-  __shared__ YbCD s_rcd[LZQ_ODE_YBREC && !kChiOnly ? kOdeBlock / 64 : 1][64];
-  __shared__ YbW s_rw[LZQ_ODE_YBREC && !kChiOnly ? kOdeBlock / 64 : 1][64];
+  __shared__ YbCD s_rcd[!kChiOnly ? kOdeBlock / 64 : 1][64];
+  __shared__ YbW s_rw[!kChiOnly ? kOdeBlock / 64 : 1][64];
   // Lanes past the end of the batch are clones of their wavefront's first point (they compute
   // it again and write nothing), so a partial wavefront -- a single CLI point included -- is
   // still full and can run cooperatively.
@@ -366,7 +402,7 @@ __global__ __launch_bounds__(kOdeBlock, LZQ_ODE_MIN_WAVES) void ode_integrate_ke
     const double xb = branch_x(o, x0, x1);
     const double xb_below = nextafter(xb, -INFINITY);  // where a split step's first part ends
     const RadauH hA = radau_h(R, h);
-    const bool riccati = LZQ_ODE_PREDICT && !kLin && o.sigmav != 0.0;  // kLin: sigma_v = 0 on every lane
+    const bool riccati = !kLin && o.sigmav != 0.0;  // kLin: sigma_v = 0 on every lane
     double Zs[3] = {Ychi, Ychi, Ychi}, Yp = Ychi;  // previous step's start and stages (predictor)
     bool have = false, done = false;
     if (!first) {  // continue from the previous launch's state
@@ -399,7 +435,7 @@ __global__ __launch_bounds__(kOdeBlock, LZQ_ODE_MIN_WAVES) void ode_integrate_ke
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     int G = 0;             // cooperative segment width (0: per-lane)
     bool tab_vary = false;  // the segment's points read different spline tables
-    if (LZQ_ODE_COOP && coop_on && __ballot(1) == ~0ull) {
+    if (coop_on && __ballot(1) == ~0ull) {
       for (int g = 64; g >= LZQ_ODE_MIN_GROUP && G == 0; g >>= 1) {
         auto same = [g](double v) {  // bit-equal to the value of the first lane of the g-segment
           const uint64_t b = __builtin_bit_cast(uint64_t, v);
@@ -421,18 +457,18 @@ __global__ __launch_bounds__(kOdeBlock, LZQ_ODE_MIN_WAVES) void ode_integrate_ke
     const int seg = lane & ~(G - 1);  // first LDS row of this lane's segment (G > 0)
     // this lane's a of a shared row's stage (its own table in a table-varying segment)
     auto row_a = [&](const StageBase& b) -> double { return tab_vary ? spline_at(w, b.s, b.k) * b.ap : b.a; };
-    // Y_B's step maps shared by the segment when it has one Gamma_wash (LZQ_ODE_YBREC)
+    // Y_B's step maps shared by the segment when it has one Gamma_wash
     bool rec_shared = false;
-    if (LZQ_ODE_YBREC && !kChiOnly && coop) {
+    if (!kChiOnly && coop) {
       const uint64_t gb = __builtin_bit_cast(uint64_t, o.gamma_w);
       rec_shared = __all(gb == __builtin_bit_cast(uint64_t, __shfl(o.gamma_w, 0, G)));
     }
-    // Linear waves (LZQ_ODE_LINFAST): with sigma_v = 0 on every lane, Y_chi's Radau step is
+    // Linear waves: with sigma_v = 0 on every lane, Y_chi's Radau step is
     // radau_step's linear branch, Z_3 = Y - sum_j hA_3j S_j with S_j = P flux a_j when depleting and
     // +0 otherwise (then Y_chi is unchanged, exactly), and Y_B's is the segment's shared map: a
     // regular step is one fma on the LDS row (+ three with depletion) -- the general path's
     // operations on the same values, hence the same bits.  Split steps take the general path.
-    const bool lin_wave = LZQ_ODE_LINFAST && LZQ_ODE_YBREC && !kChiOnly && rec_shared && __all(o.sigmav == 0.0);
+    const bool lin_wave = !kChiOnly && rec_shared && __all(o.sigmav == 0.0);
     if (lin_wave != kLin) return;  // the other variant of this launch steps this wavefront
     const bool lin_fast = kLin;
     // Linear waves: the first split step (xk < xb <= xk + h), found once.  x_k's rounding error is
@@ -449,7 +485,7 @@ __global__ __launch_bounds__(kOdeBlock, LZQ_ODE_MIN_WAVES) void ode_integrate_ke
       const double xq = x0 + (double)(k_begin - 1) * h;
       prev_split = xq < xb && xb <= xq + h;
     }
-    if ((lin_fast || LZQ_ODE_NOSPLITVAR) && xb < INFINITY) {  // branch_x: +inf when no step splits
+    if (xb < INFINITY) {  // branch_x: +inf when no step splits
       const double kf = floor((xb - x0) / h);
       const double margin = 2.0 + floor(8.0 * __DBL_EPSILON__ * (fabs(x0) + fabs(x1)) / h);
       if (!(margin <= 16.0)) {
@@ -467,25 +503,21 @@ __global__ __launch_bounds__(kOdeBlock, LZQ_ODE_MIN_WAVES) void ode_integrate_ke
         }
       }
     }
-    // Split-free waves (LZQ_ODE_NOSPLITVAR): when no lane of the wave has a split step in this
+    // Split-free waves: when no lane of the wave has a split step in this
     // launch's range (the window does not reach T = m/3, or the split lies in another
     // continuation launch), the <kNoSplit> variant steps the wave: the same operations with the
     // split paths compiled out, whose mere presence costs ~11% of a stiff / Riccati step
     // (register pressure).  Both variants evaluate the same wave-uniform predicate.
-    if (!kLin && LZQ_ODE_NOSPLITVAR) {
+    if (!kLin) {
       const bool lane_ns = k_split == INT64_MAX || (k_split >= 0 && (k_split + 1 < k_begin || k_split >= k_stop));
       if (__all(lane_ns) != kNoSplit) return;
       // whole-wave cooperative, one table, one Gamma_wash: ode_riccati_kernel steps it, split steps
       // included unless the x rounding makes the split search unreliable (k_split = -1: every step
-      // takes the general path here) -- LZQ_ODE_RICVAR; the same predicate there, on the same values
-      if (LZQ_ODE_RICVAR && !kChiOnly && G == 64 && (!tab_vary || LZQ_ODE_RICTAB) && rec_shared &&
-          __all(k_split != -1))
-        return;
+      // takes the general path here); the same predicate there, on the same values
+      if (!kChiOnly && G == 64 && (!tab_vary || LZQ_ODE_RICTAB) && rec_shared && __all(k_split != -1)) return;
       // and waves of narrower uniform segments, one table and one Gamma_wash each:
-      // ode_riccati_kernel<., false, true> (LZQ_ODE_RICSEG)
-      if (LZQ_ODE_RICVAR && LZQ_ODE_RICSEG && !kChiOnly && G > 0 && G < 64 && !tab_vary && rec_shared &&
-          __all(k_split != -1))
-        return;
+      // ode_riccati_kernel<., false, true>
+      if (!kChiOnly && G > 0 && G < 64 && !tab_vary && rec_shared && __all(k_split != -1)) return;
     }
     // Row tables (OdeRows): a whole linear wave of one run, no depletion (its rows would need the
     // stage a_j too), whose run's representative agrees with every lane in the fill's inputs --
@@ -493,7 +525,7 @@ __global__ __launch_bounds__(kOdeBlock, LZQ_ODE_MIN_WAVES) void ode_integrate_ke
     // run's rows instead of filling its own (the same values: ode_rows_kernel's operations are the
     // fill's).  Regular steps off the tight loop (after a split) then form their stages per lane.
     const YbCD* rrow = nullptr;
-    if (kLin && LZQ_ODE_ROWS && rws.rows && G == 64) {
+    if (kLin && rws.rows && G == 64) {
       const int32_t ru = rws.run_of[i];
       if (__all(ru >= 0 && (int64_t)ru < rws.n_runs && ru == __shfl(ru, 0, 64) && !o.deplete)) {
         const int64_t rep = rws.run_rep[ru], r0 = rws.row_off[ru], r1 = rws.row_off[ru + 1];
@@ -512,29 +544,18 @@ __global__ __launch_bounds__(kOdeBlock, LZQ_ODE_MIN_WAVES) void ode_integrate_ke
       }
     }
     // Row-table waves stage their run's rows in their wave's s_base slot (unused by them: their
-    // stages are per lane off the tight loop), kOdeRowBlk rows per block in two buffers: block
-    // i + 1's rows are fetched straight into LDS (global_load_lds, 16 B per lane, no registers)
-    // while block i steps, so the global latency is off the step chain.
-    // (LZQ_ODE_ROWS_ASYNC = 0: one buffer of twice the rows, staged through registers, 4 loads in flight)
-    constexpr int kOdeRowBlk = LZQ_ODE_ROWS_ASYNC ? LZQ_ODE_ROWS_BLOCK : 2 * LZQ_ODE_ROWS_BLOCK;
-    static_assert(sizeof(s_base[0]) >= (LZQ_ODE_ROWS_ASYNC ? 2 : 1) * kOdeRowBlk * sizeof(YbCD),
-                  "row buffers exceed the s_base slot");
+    // stages are per lane off the tight loop), kOdeRowBlk rows per block in one buffer, staged
+    // through registers with LZQ_ODE_ROWS_COPY loads in flight.  (Two buffers of half the rows, the
+    // next block fetched straight into LDS while a block steps, measured slower: DESIGN §7.)
+    constexpr int kOdeRowBlk = 2 * LZQ_ODE_ROWS_BLOCK;
+    static_assert(sizeof(s_base[0]) >= kOdeRowBlk * sizeof(YbCD), "the row buffer exceeds the s_base slot");
     static_assert(kOdeRowBlk % 64 == 0, "row blocks are whole wavefront fetches");
     YbCD* const s_rows = reinterpret_cast<YbCD*>(&s_base[wv][0][0]);
-    const bool rowblk = kLin && LZQ_ODE_ROWS && rrow;
+    const bool rowblk = kLin && rrow;
     const int64_t block = rowblk ? kOdeRowBlk : (coop ? G : N);
-    // rows kf .. kf + kOdeRowBlk - 1 (those < k_stop) into dst; lane l's row of each 64 lands at dst + 64 j + l
-    auto fetch_rows = [&](int64_t kf, YbCD* dst) {
-#pragma unroll
-      for (int j = 0; j < kOdeRowBlk / 64; ++j)
-        if (kf + 64 * j + lane < k_stop)
-          __builtin_amdgcn_global_load_lds(rrow + kf + 64 * j + lane, dst + 64 * j, 16, 0, 0);
-    };
-    if (LZQ_ODE_ROWS_ASYNC && rowblk) fetch_rows(k_begin, s_rows);
-    YbCD* s_cur = s_rows;  // row-table waves: this block's buffer
     for (int64_t kb = k_begin; kb < k_stop; kb += block) {
       const int64_t kend = kb + block < k_stop ? kb + block : k_stop;
-      if (rowblk && !LZQ_ODE_ROWS_ASYNC) {
+      if (rowblk) {
         // groups of LZQ_ODE_ROWS_COPY loads, all issued before the group's first store (the empty
         // asm consumes the whole group; guarded per row, the compiler waited on each load before
         // its store); rows past the run's end read its last row, into LDS slots no step reads
@@ -554,15 +575,6 @@ __global__ __launch_bounds__(kOdeBlock, LZQ_ODE_MIN_WAVES) void ode_integrate_ke
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      } else if (rowblk) {
-        s_cur = s_rows + (((kb - k_begin) / kOdeRowBlk) & 1) * kOdeRowBlk;
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this block's rows have landed in LDS
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // the next block's rows into the other buffer (its last reader was the previous block, whose
-        // steps ended at that block's closing wave barrier)
-        if (kb + kOdeRowBlk < k_stop) fetch_rows(kb + kOdeRowBlk, s_rows + kOdeRowBlk - (s_cur - s_rows));
       } else if (coop) {
         const int64_t kl = kb + (lane - seg);
         if (kl < kend) {
@@ -574,14 +586,14 @@ __global__ __launch_bounds__(kOdeBlock, LZQ_ODE_MIN_WAVES) void ode_integrate_ke
                                              : ode_stage_base(o, w, xk + R.c[j] * h);
             s_base[wv][lane][j] = bs[j];
           }
-          if (LZQ_ODE_YBREC && !kChiOnly && rec_shared) {
+          if (!kChiOnly && rec_shared) {
             // beta_j as stage_scale forms it (Gamma_wash * base), a_j the base: the step map (its d
             // is this lane's; a table-varying segment's lanes form theirs from W and id)
             const double beta[3] = {o.gamma_w * bs[0].beta, o.gamma_w * bs[1].beta, o.gamma_w * bs[2].beta};
             const double a[3] = {bs[0].a, bs[1].a, bs[2].a};
             const YbRec yr = yb_rec(hA, beta, a);
-            s_rcd[LZQ_ODE_YBREC && !kChiOnly ? wv : 0][lane] = {yr.c, yr.d};
-            s_rw[LZQ_ODE_YBREC && !kChiOnly ? wv : 0][lane] = {{yr.W[0], yr.W[1], yr.W[2]}, yr.id};
+            s_rcd[!kChiOnly ? wv : 0][lane] = {yr.c, yr.d};
+            s_rw[!kChiOnly ? wv : 0][lane] = {{yr.W[0], yr.W[1], yr.W[2]}, yr.id};
           }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -597,8 +609,8 @@ __global__ __launch_bounds__(kOdeBlock, LZQ_ODE_MIN_WAVES) void ode_integrate_ke
           const int nf = (int)(kg - k);
           if (nf > 0) {
             const int r0 = seg + (int)(k - kb);
-            const YbCD* rr = rowblk ? &s_cur[k - kb] : &s_rcd[LZQ_ODE_YBREC && !kChiOnly ? wv : 0][r0];
-            const YbW* rw = &s_rw[LZQ_ODE_YBREC && !kChiOnly ? wv : 0][r0];
+            const YbCD* rr = rowblk ? &s_rows[k - kb] : &s_rcd[!kChiOnly ? wv : 0][r0];
+            const YbW* rw = &s_rw[!kChiOnly ? wv : 0][r0];
             if (tab_vary) {  // each step's a_j from this lane's table, then its own d
               // T falls with x, so the rows' spline intervals run from the first row's stage 0
               // down to the last row's stage 2; when they are one interval (the rule on long
@@ -652,7 +664,7 @@ __global__ __launch_bounds__(kOdeBlock, LZQ_ODE_MIN_WAVES) void ode_integrate_ke
           }
           if (k >= kend) break;
         }
-        const double xk = x0 + (LZQ_ODE_KD ? kd : (double)k) * h;
+        const double xk = x0 + kd * h;
         // (kNoSplit: no step of this launch splits on any lane of the wave -- the split paths compile away)
         const bool split = !kNoSplit && xk < xb && xb <= xk + h;  // the last stage (x = xk + h) would see the other branch
         const double xa = split ? xb_below : xk + h;
@@ -691,22 +703,22 @@ __global__ __launch_bounds__(kOdeBlock, LZQ_ODE_MIN_WAVES) void ode_integrate_ke
               sg[j] = (kChiOnly && !o.deplete) ? ode_stage_chi(o, xk + R.c[j] * hs) : ode_stage(o, w, xk + R.c[j] * hs);
           }
           if (riccati && !split && !pred_step(k)) use_guess = block_guess(R, hs, sg, Ychi, Zs);
-          if (LZQ_ODE_YBREC && !kChiOnly) {  // Y_B by its step map, then Y_chi alone
+          if (!kChiOnly) {  // Y_B by its step map, then Y_chi alone
             YbCD r;
             if (rowblk && !split) {
-              r = s_cur[k - kb];
+              r = s_rows[k - kb];
             } else if (rec_shared && !split) {
-              r = s_rcd[LZQ_ODE_YBREC && !kChiOnly ? wv : 0][seg + (k - kb)];
+              r = s_rcd[!kChiOnly ? wv : 0][seg + (k - kb)];
               if (tab_vary) {
                 const double a[3] = {sg[0].a, sg[1].a, sg[2].a};
-                r.d = yb_d(s_rw[LZQ_ODE_YBREC && !kChiOnly ? wv : 0][seg + (k - kb)], a);
+                r.d = yb_d(s_rw[!kChiOnly ? wv : 0][seg + (k - kb)], a);
               }
             } else {
               const YbRec yr = yb_rec(split ? radau_h(R, hs) : hA, sg);
               r = {yr.c, yr.d};
             }
             YB = __builtin_fma(r.c, YB, o.Pf * r.d);
-            if (LZQ_ODE_GEN_RICSTEP && !split) {  // the same operations through ric_step (see there)
+            if (!split) {  // the same operations through ric_step (see there)
               double lam[3], E2[3], S[3];
 #pragma unroll
               for (int j = 0; j < 3; ++j) {
@@ -722,7 +734,7 @@ __global__ __launch_bounds__(kOdeBlock, LZQ_ODE_MIN_WAVES) void ode_integrate_ke
               ok = radau_step<false>(split ? radau_h(R, hs) : hA, sg, Ychi, YB, Zs, use_guess);
             }
           } else {
-            ok = radau_step<!kChiOnly>(split ? radau_h(R, hs) : hA, sg, Ychi, YB, Zs, use_guess);
+            ok = radau_step<false>(split ? radau_h(R, hs) : hA, sg, Ychi, YB, Zs, use_guess);
           }
         }
         if (ok && split && xk + h > xb) {
@@ -732,12 +744,12 @@ __global__ __launch_bounds__(kOdeBlock, LZQ_ODE_MIN_WAVES) void ode_integrate_ke
 #pragma unroll
           for (int j = 0; j < 3; ++j)
             sg[j] = (kChiOnly && !o.deplete) ? ode_stage_chi(o, xb + R.c[j] * hs) : ode_stage(o, w, xb + R.c[j] * hs);
-          if (LZQ_ODE_YBREC && !kChiOnly) {
+          if (!kChiOnly) {
             const YbRec r = yb_rec(radau_h(R, hs), sg);  // the split step's second part
             YB = __builtin_fma(r.c, YB, o.Pf * r.d);
             ok = radau_step<false>(radau_h(R, hs), sg, Ychi, YB, Zs, false);
           } else {
-            ok = radau_step<!kChiOnly>(radau_h(R, hs), sg, Ychi, YB, Zs, false);
+            ok = radau_step<false>(radau_h(R, hs), sg, Ychi, YB, Zs, false);
           }
         }
         have = !split;   // the predictor needs a full regular step behind it
@@ -822,7 +834,7 @@ __global__ __launch_bounds__(kOdeBlock) void ode_rows_kernel(const lzq_point* __
 }
 
 // ---------------------------------------------------------------------------------------
-// ode_riccati_kernel (LZQ_ODE_RICVAR): the <kNoSplit> variant's steps for its most common wave,
+// ode_riccati_kernel: the <kNoSplit> variant's steps for its most common wave,
 // a whole 64-lane cooperative segment (G = 64) on one spline table with one Gamma_wash and no
 // split step in the launch -- the Riccati sweeps over sigma_v, P, flux, deplete (and m_chi
 // once grouped).  Every lane of such a wave agrees in everything ode_stage_base reads, so those
@@ -840,25 +852,6 @@ __global__ __launch_bounds__(kOdeBlock) void ode_rows_kernel(const lzq_point* __
 struct RicRow {
   double lam[3], E2[3], a[3];  // StageBase lam, E2, a of the step's three stages
 };
-
-#ifndef LZQ_RIC_KRELOAD
-#define LZQ_RIC_KRELOAD 1  // ode_riccati_kernel's lean loop reloads the predictor constants per step (SGPR room)
-#endif
-#ifndef LZQ_RIC_TAB_MIN_WAVES
-#define LZQ_RIC_TAB_MIN_WAVES 3  // its rows take 38 KB of LDS per 4-wave block: 3 blocks per CU
-#endif
-#ifndef LZQ_RIC_IP
-#define LZQ_RIC_IP 2  // ode_riccati_kernel's lean steps through ric_step_ip (round 6; see there); 2: have / Yp outside the joins
-#endif
-#ifndef LZQ_RIC_KPTR
-#define LZQ_RIC_KPTR 1  // the predictor table's address hoisted out of the step loop (see there)
-#endif
-#ifndef LZQ_RIC_V4
-#define LZQ_RIC_V4 1  // ric_newton's dmax without the +0 start (same tests; see there)
-#endif
-#ifndef LZQ_RIC_LEAN
-#define LZQ_RIC_LEAN 1  // ode_riccati_kernel's regular steps through ric_step (round 6): radau_step<false>'s operations, lean registers
-#endif
 
 // ode_riccati_kernel's cooperative fill of one row (step at xk): the stage bases, beta_j and the
 // Y_B step map, with the operations of the kernel's inline fill (ode_stage_base, yb_rec on
@@ -949,7 +942,7 @@ __device__ __forceinline__ bool ric_newton(double (&Z)[3], double Y0, const doub
     J.b[2][0] = fma_neg_s(k[1], kRadauAinv[2][0], pv[4]), J.b[2][1] = fma_neg_s(k[0], kRadauAinv[2][1], pv[5]);
     J.b[2][2] = FMA(k[0], k[1], -kRadauAinvP[8]);
     const double den = FMA(k[0], J.b[0][0], FMA(kRadauAinv[0][1], J.b[1][0], kRadauAinv[0][2] * J.b[2][0]));
-    J.id = LZQ_ODE_NEWTON_RCP ? rcp_pos(den) : 1.0 / den;
+    J.id = rcp_pos(den);
   }
   double g[3];
 #pragma unroll
@@ -964,8 +957,7 @@ __device__ __forceinline__ bool ric_newton(double (&Z)[3], double Y0, const doub
   // newton_j's dmax = fmax(fmax(fmax(+0, |g0|), |g1|), |g2|) without the +0: the two differ only when
   // all three corrections are NaN (+0 there, NaN here), and both then fail "dmax > c zmax" (zmax >= 0),
   // so near and the convergence test are the same
-  const double dmax = LZQ_RIC_V4 ? fmax(fmax(fabs(g[0]), fabs(g[1])), fabs(g[2]))
-                                 : fmax(fmax(fmax(0.0, fabs(g[0])), fabs(g[1])), fabs(g[2]));
+  const double dmax = fmax(fmax(fabs(g[0]), fabs(g[1])), fabs(g[2]));
   near = !(dmax > 1e-3 * zmax);
   return !(dmax > 1e-15 * zmax);
 }
@@ -1095,8 +1087,7 @@ ode_riccati_kernel(const lzq_point* __restrict__ pts, const lzq_ode_params* __re
   __shared__ double s_beta[kOdeBlock / 64][64][3];  // the fill's beta_j (Gamma_wash * base)
   static_assert(!kSeg || !kTab, "segment waves: one table per segment");
 
-  if (!LZQ_ODE_RICVAR || !LZQ_ODE_COOP || !coop_on) return;
-  if (kSeg && !LZQ_ODE_RICSEG) return;
+  if (!coop_on) return;
   // --- the classification of ode_integrate_kernel<false, false, true>, on the same values ---
   const int64_t wave0 = (int64_t)blockIdx.x * kOdeBlock + (threadIdx.x & ~63);
   if (wave0 >= n) return;
@@ -1113,7 +1104,7 @@ ode_riccati_kernel(const lzq_point* __restrict__ pts, const lzq_ode_params* __re
   // ode_integrate_kernel<kLin>'s) and, for whole waves, one of the other table class.  Evaluated on
   // the lanes still here; with one missing the ballot below returns anyway, so neither exits a wave
   // this kernel would step.
-  if (LZQ_ODE_LINFAST && __all(pymax(ode[i].sigma_v_chi_GeV_m2, 0.0) == 0.0)) return;
+  if (__all(pymax(ode[i].sigma_v_chi_GeV_m2, 0.0) == 0.0)) return;
   if (!kSeg) {
     const uint64_t wb = (uint64_t)(uintptr_t)w;
     if (__all(wb == __builtin_bit_cast(uint64_t, __shfl(__builtin_bit_cast(double, wb), 0, 64))) == kTab) return;
@@ -1147,7 +1138,7 @@ ode_riccati_kernel(const lzq_point* __restrict__ pts, const lzq_ode_params* __re
   if (__all(same(__builtin_bit_cast(double, w))) == kTab) return;            // tab_vary: the kTab kernel's
   if (kTab && !LZQ_ODE_RICTAB) return;
   if (!__all(same(o.gamma_w))) return;                                       // !rec_shared
-  if (LZQ_ODE_LINFAST && __all(o.sigmav == 0.0)) return;                     // lin_wave
+  if (__all(o.sigmav == 0.0)) return;                                        // lin_wave
   const int64_t N = (int64_t)steps;
   const int64_t k_begin = cont ? k_lo : 0;
   const int64_t k_stop = cont ? (k_lo + k_cnt < N ? k_lo + k_cnt : N) : N;
@@ -1218,7 +1209,7 @@ ode_riccati_kernel(const lzq_point* __restrict__ pts, const lzq_ode_params* __re
     Ychi = n_chi_eq(o.T_hi, m, pt.g_chi, pt.stats) / s_entropy(o.T_hi, pt.g_star_s);
   }
   double YB = 0.0;
-  const bool riccati = LZQ_ODE_PREDICT && sigmav != 0.0;
+  const bool riccati = sigmav != 0.0;
   double Zs[3] = {Ychi, Ychi, Ychi}, Yp = Ychi;
   bool have = false, done = false;
   if (!first) {
@@ -1293,7 +1284,7 @@ ode_riccati_kernel(const lzq_point* __restrict__ pts, const lzq_ode_params* __re
   const double hA2[3] = {hA.a[2][0], hA.a[2][1], hA.a[2][2]};
   const bool dep_any = !__all(deplete == 0);  // wave-uniform: some lane depletes its source
   double pv[6] = {kRadauAinvP[1], kRadauAinvP[2], kRadauAinvP[3], kRadauAinvP[5], kRadauAinvP[6], kRadauAinvP[7]};
-  if (LZQ_RIC_LEAN && kPhase != 1) {
+  if (kPhase != 1) {
 #pragma unroll
     for (int q = 0; q < 6; ++q) asm volatile("" : "+v"(pv[q]));
   }
@@ -1307,54 +1298,35 @@ ode_riccati_kernel(const lzq_point* __restrict__ pts, const lzq_ode_params* __re
     uint64_t xok = 0;
     {  // lane l: the stage ingredients and Y_B step map of step kb + l (the cooperative fill)
       const int64_t kl = kb + (lane - seg);
-      if (LZQ_RIC_LEAN) {
-        // the steps' x guard (xk + h > xk, wave-uniform per step) as one mask, from the fill's xk
-        const double xk = x0u + (double)kl * hu;
-        xok = __ballot(kl < kend && xk + hu > xk);
-      }
+      // the steps' x guard (xk + h > xk, wave-uniform per step) as one mask, from the fill's xk
+      const double xk = x0u + (double)kl * hu;
+      xok = __ballot(kl < kend && xk + hu > xk);
       if (kl < kend) {
         if (kTab) {
           ric_fill_tab(&ou, wu, x0u + (double)kl * hu, hu, &s_rowt[wv][lane], s_beta[wv][lane]);
-        } else if (LZQ_RIC_LEAN) {
-          ric_fill(&ou, wu, x0u + (double)kl * hu, hu, &s_row[wv][lane], s_beta[wv][lane], &s_rcd[wv][lane]);
         } else {
-        const double xk = x0u + (double)kl * hu;
-        RicRow& row = s_row[wv][lane];
-        double* bt = s_beta[wv][lane];
-#pragma unroll 1
-        for (int j = 0; j < 3; ++j) {  // one stage at a time (the fill's register peak), parked in LDS
-          const double cj = j == 0 ? R.c[0] : (j == 1 ? R.c[1] : R.c[2]);  // (a dynamic index would go to scratch)
-          const StageBase bs = ode_stage_base(ou, wu, xk + cj * hu);
-          row.lam[j] = bs.lam;
-          row.E2[j] = bs.E2;
-          row.a[j] = bs.a;
-          bt[j] = ou.gamma_w * bs.beta;
-        }
-        const double beta[3] = {bt[0], bt[1], bt[2]}, a[3] = {row.a[0], row.a[1], row.a[2]};
-        const YbRec yr = yb_rec(hA, beta, a);
-        s_rcd[wv][lane] = {yr.c, yr.d};
+          ric_fill(&ou, wu, x0u + (double)kl * hu, hu, &s_row[wv][lane], s_beta[wv][lane], &s_rcd[wv][lane]);
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
-    double kd = (double)kb;
     // the block's predictor-free step (k = 0 mod LZQ_ODE_PRED_BLOCK) is row rz (a row past the
     // block when it has none: pass 2 starts after the split steps, unaligned): one wave-uniform
     // compare per step.  (Peeling row 0 of aligned blocks, with pass 1 run on to the next block,
     // measured slower: profiles/round5/ablate_ode_pred_block.json.)
     const int rz = (int)((-kb) & (int64_t)(LZQ_ODE_PRED_BLOCK - 1));
-    // LZQ_RIC_KPTR: the predictor table's address formed once per block of steps (two SGPRs), so a
-    // step's reload is the constants' own scalar loads, not a GOT load and then them
+    // the predictor table's address formed once per block of steps (two SGPRs), so a step's reload
+    // is the constants' own scalar loads, not a GOT load and then them
     const __attribute__((address_space(4))) double* kp_loop =
         (const __attribute__((address_space(4))) double*)&kRadauPred[0][0];
-    if (LZQ_RIC_KPTR) asm volatile("" : "+s"(kp_loop));  // opaque: not re-formed in the loop
-    // a wave with no depleting lane runs the loop without the source products (ric_step<false>)
+    asm volatile("" : "+s"(kp_loop));  // opaque: not re-formed in the loop
+    // a wave with no depleting lane runs the loop without the source products (ric_step_ip<false>)
     auto lean_steps = [&](auto dep_tag) {
     constexpr bool kDep = decltype(dep_tag)::value;
-    // LZQ_RIC_V4: a uniform trip count, each lane's steps under !done (a lane whose Newton iteration
-    // failed stops there, as in the loop below)
+    // a uniform trip count, each lane's steps under !done (a lane whose Newton iteration failed stops
+    // there, as in the loop below)
     const int nr = kend > kb ? (int)(kend - kb) : 0;  // kSeg: this segment's steps in the block
     if (LZQ_RIC_IP || kTab || kSeg) {
       // the same steps with the loop-carried values written once each (ric_step_ip): the predictor
@@ -1372,7 +1344,7 @@ ode_riccati_kernel(const lzq_point* __restrict__ pts, const lzq_ode_params* __re
         // a lane that is not done has taken steps 0 .. r - 1 of this block, so have = have || r > 0
         if (riccati && (LZQ_RIC_IP < 2 || r > 0 || have) && (LZQ_RIC_IP >= 2 || have) && r != rz) {
           const __attribute__((address_space(4))) double* kp = kp_loop;
-          if (LZQ_RIC_KRELOAD) asm volatile("" : "+s"(kp));
+          asm volatile("" : "+s"(kp));  // reloaded per step, not held in 24 SGPRs across the loop
           use_guess = true;
 #pragma unroll
           for (int j = 0; j < 3; ++j) {
@@ -1442,7 +1414,7 @@ ode_riccati_kernel(const lzq_point* __restrict__ pts, const lzq_ode_params* __re
       if (done && !done0) st = LZQ_ODE_NEWTON;
       return;
     }
-    for (int r = 0; r < nr && (LZQ_RIC_V4 || !done); ++r) {
+    for (int r = 0; r < nr; ++r) {
       // the same step as the loop below: the row is read first (its LDS latency under the
       // predictor), the x guard is the fill's mask bit, the step index needs no counter
       const RicRow row = s_row[wv][r];
@@ -1453,10 +1425,11 @@ ode_riccati_kernel(const lzq_point* __restrict__ pts, const lzq_ode_params* __re
       bool use_guess = false;
       if (riccati && have && r != rz) {
         // the predictor's 12 constants are read from the constant cache each step (scalar loads
-        // through an opaque pointer) instead of held in 24 SGPRs across the loop (LZQ_RIC_KRELOAD)
-        const __attribute__((address_space(4))) double* kp = LZQ_RIC_KPTR ? kp_loop
-            : (const __attribute__((address_space(4))) double*)&kRadauPred[0][0];
-        if (LZQ_RIC_KRELOAD) asm volatile("" : "+s"(kp));
+        // through an opaque pointer) instead of held in 24 SGPRs across the loop; this loop forms
+        // the table's address itself
+        const __attribute__((address_space(4))) double* kp =
+            (const __attribute__((address_space(4))) double*)&kRadauPred[0][0];
+        asm volatile("" : "+s"(kp));
         double g[3];
         use_guess = true;
 #pragma unroll
@@ -1498,60 +1471,8 @@ ode_riccati_kernel(const lzq_point* __restrict__ pts, const lzq_ode_params* __re
       }
     }
     };
-    if (LZQ_RIC_LEAN) {
-      if (dep_any) lean_steps(std::true_type{});
-      else lean_steps(std::false_type{});
-    }
-    for (int r = 0; !LZQ_RIC_LEAN && r < (int)(kend - kb) && !done; ++r) {
-      const double xk = x0u + kd * hu;
-      kd += 1.0;
-      const double YB_prev = YB;
-      const double Ystart = Ychi;
-      bool use_guess = false;
-      if (riccati && have && r != rz) {  // the Radau5 predictor, as ode_integrate_kernel
-        double g[3];
-        use_guess = true;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          g[j] = fma_s(Zs[2], kRadauPred[j][3], fma_s(Zs[1], kRadauPred[j][2],
-                                                      fma_s(Zs[0], kRadauPred[j][1], kRadauPred[j][0] * Yp)));
-          use_guess = use_guess && fabs(g[j] - Ychi) <= 0.25 * fabs(Ychi);
-        }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) Zs[j] = g[j];
-      }
-      bool ok = true;
-      if (xk + hu > xk) {
-        const RicRow& row = s_row[wv][r];
-        OdeStage sg[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {  // stage_scale's products (beta is not read by radau_step<false>)
-          sg[j].alpha = Pf * row.a[j];
-          sg[j].S = deplete ? sg[j].alpha : 0.0;
-          sg[j].lam = sigmav * row.lam[j];
-          sg[j].E2 = row.E2[j];
-          sg[j].beta = 0.0;
-          sg[j].a = row.a[j];
-        }
-        const YbCD rc = s_rcd[wv][r];
-        YB = __builtin_fma(rc.c, YB, Pf * rc.d);
-        if (riccati && r == rz) use_guess = block_guess(R, hu, sg, Ychi, Zs);
-        if (LZQ_RIC_LEAN) {
-          const double lam[3] = {sg[0].lam, sg[1].lam, sg[2].lam}, E2[3] = {sg[0].E2, sg[1].E2, sg[2].E2},
-                       S[3] = {sg[0].S, sg[1].S, sg[2].S};
-          ok = ric_step<true>(hu, hA2, lam, E2, S, pv, Ychi, Zs, use_guess);
-        } else {
-          ok = radau_step<false>(hA, sg, Ychi, YB, Zs, use_guess);
-        }
-      }
-      have = true;
-      Yp = Ystart;
-      if (!ok) {
-        YB = YB_prev;
-        st = LZQ_ODE_NEWTON;
-        done = true;
-      }
-    }
+    if (dep_any) lean_steps(std::true_type{});
+    else lean_steps(std::false_type{});
     __builtin_amdgcn_wave_barrier();  // every lane is done with this block's rows
   }
   const bool finished = finished_here || done;
@@ -1605,12 +1526,6 @@ __constant__ double kGLx[8] = {-0x1.ebab1cb0acc66p-1, -0x1.97e4ab249f41ep-1, -0x
 __constant__ double kGLw[8] = {0x1.9ea1d04ca0393p-4, 0x1.c76fb531d2b91p-3, 0x1.413c50a255611p-2, 0x1.736360b19933fp-2,
                                0x1.736360b19933fp-2, 0x1.413c50a255611p-2, 0x1.c76fb531d2b91p-3, 0x1.9ea1d04ca0393p-4};
 constexpr int kQuadMaxSub = 4096;  // per knot interval; beyond: status LZQ_ODE_UNRESOLVED
-#ifndef LZQ_QUAD_UNROLL
-#define LZQ_QUAD_UNROLL 1
-#endif
-#ifndef LZQ_QUAD_MIN_WAVES
-#define LZQ_QUAD_MIN_WAVES 3
-#endif
 
 // alpha(x) dx/dT = (SB/s)/(H x) * m/T^2 at T (inside knot interval k with PPoly coefficients c,
 // knot Tk), with the operations of ode_stage.
@@ -1620,7 +1535,7 @@ __device__ __forceinline__ double ode_alpha_dT(const OdePoint& o, const double* 
   const double T3 = (T * T) * T;
   const double s = pymax(o.s0 * T3, 1e-300);
   const double qT = o.Tp * iT;
-  const double y = 0.5 * o.B * (LZQ_ODE_FMA ? __builtin_fma(qT, qT, -1.0) : qT * qT - 1.0);
+  const double y = 0.5 * o.B * __builtin_fma(qT, qT, -1.0);
   const double q = y * o.inv_sig;
   const double window = exp_nonpos(-0.5 * (q * q));
   double n_eq, vbar;
@@ -1814,66 +1729,64 @@ int launch_integrate(const lzq_point* d_points, const lzq_ode_params* d_ode, int
                        d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status, lzq::g_ode_coop, k_lo, k_cnt,
                        st, d_skip, rw);
     int rc = hip_check(hipGetLastError(), fn);
-    if constexpr (LZQ_ODE_NOSPLITVAR) {
+    if (rc != LZQ_OK) return rc;
+    hipLaunchKernelGGL((lzq::ode_integrate_kernel<kChiOnly, false, true>), dim3((unsigned)ode_blocks(n)),
+                       dim3(lzq::kOdeBlock), 0, s, d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status,
+                       lzq::g_ode_coop, k_lo, k_cnt, st, d_skip, rw);
+    rc = hip_check(hipGetLastError(), fn);
+    if constexpr (!kChiOnly) {  // the three passes (ode_riccati_kernel)
       if (rc != LZQ_OK) return rc;
-      hipLaunchKernelGGL((lzq::ode_integrate_kernel<kChiOnly, false, true>), dim3((unsigned)ode_blocks(n)),
-                         dim3(lzq::kOdeBlock), 0, s, d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status,
-                         lzq::g_ode_coop, k_lo, k_cnt, st, d_skip, rw);
+      hipLaunchKernelGGL(lzq::ode_riccati_kernel<0>, dim3((unsigned)ode_blocks(n)), dim3(lzq::kOdeBlock), 0, s,
+                         d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status, lzq::g_ode_coop, k_lo,
+                         k_cnt, st, d_skip);
       rc = hip_check(hipGetLastError(), fn);
-      if constexpr (LZQ_ODE_RICVAR && !kChiOnly) {  // the three passes (ode_riccati_kernel)
+      if (rc != LZQ_OK) return rc;
+      hipLaunchKernelGGL(lzq::ode_riccati_kernel<1>, dim3((unsigned)ode_blocks(n)), dim3(lzq::kOdeBlock), 0, s,
+                         d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status, lzq::g_ode_coop, k_lo,
+                         k_cnt, st, d_skip);
+      rc = hip_check(hipGetLastError(), fn);
+      if (rc != LZQ_OK) return rc;
+      hipLaunchKernelGGL(lzq::ode_riccati_kernel<2>, dim3((unsigned)ode_blocks(n)), dim3(lzq::kOdeBlock), 0, s,
+                         d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status, lzq::g_ode_coop, k_lo,
+                         k_cnt, st, d_skip);
+      rc = hip_check(hipGetLastError(), fn);
+      // the table-varying waves' three passes (none for one point: its wave is clones of it)
+      if (LZQ_ODE_RICTAB && n > 1) {
         if (rc != LZQ_OK) return rc;
-        hipLaunchKernelGGL(lzq::ode_riccati_kernel<0>, dim3((unsigned)ode_blocks(n)), dim3(lzq::kOdeBlock), 0, s,
-                           d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status, lzq::g_ode_coop, k_lo,
+        hipLaunchKernelGGL((lzq::ode_riccati_kernel<0, true>), dim3((unsigned)ode_blocks(n)), dim3(lzq::kOdeBlock), 0,
+                           s, d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status, lzq::g_ode_coop, k_lo,
                            k_cnt, st, d_skip);
         rc = hip_check(hipGetLastError(), fn);
         if (rc != LZQ_OK) return rc;
-        hipLaunchKernelGGL(lzq::ode_riccati_kernel<1>, dim3((unsigned)ode_blocks(n)), dim3(lzq::kOdeBlock), 0, s,
-                           d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status, lzq::g_ode_coop, k_lo,
+        hipLaunchKernelGGL((lzq::ode_riccati_kernel<1, true>), dim3((unsigned)ode_blocks(n)), dim3(lzq::kOdeBlock), 0,
+                           s, d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status, lzq::g_ode_coop, k_lo,
                            k_cnt, st, d_skip);
         rc = hip_check(hipGetLastError(), fn);
         if (rc != LZQ_OK) return rc;
-        hipLaunchKernelGGL(lzq::ode_riccati_kernel<2>, dim3((unsigned)ode_blocks(n)), dim3(lzq::kOdeBlock), 0, s,
-                           d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status, lzq::g_ode_coop, k_lo,
+        hipLaunchKernelGGL((lzq::ode_riccati_kernel<2, true>), dim3((unsigned)ode_blocks(n)), dim3(lzq::kOdeBlock), 0,
+                           s, d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status, lzq::g_ode_coop, k_lo,
                            k_cnt, st, d_skip);
         rc = hip_check(hipGetLastError(), fn);
-        // the table-varying waves' three passes (none for one point: its wave is clones of it)
-        if (LZQ_ODE_RICTAB && n > 1) {
-          if (rc != LZQ_OK) return rc;
-          hipLaunchKernelGGL((lzq::ode_riccati_kernel<0, true>), dim3((unsigned)ode_blocks(n)), dim3(lzq::kOdeBlock), 0,
-                             s, d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status, lzq::g_ode_coop, k_lo,
-                             k_cnt, st, d_skip);
-          rc = hip_check(hipGetLastError(), fn);
-          if (rc != LZQ_OK) return rc;
-          hipLaunchKernelGGL((lzq::ode_riccati_kernel<1, true>), dim3((unsigned)ode_blocks(n)), dim3(lzq::kOdeBlock), 0,
-                             s, d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status, lzq::g_ode_coop, k_lo,
-                             k_cnt, st, d_skip);
-          rc = hip_check(hipGetLastError(), fn);
-          if (rc != LZQ_OK) return rc;
-          hipLaunchKernelGGL((lzq::ode_riccati_kernel<2, true>), dim3((unsigned)ode_blocks(n)), dim3(lzq::kOdeBlock), 0,
-                             s, d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status, lzq::g_ode_coop, k_lo,
-                             k_cnt, st, d_skip);
-          rc = hip_check(hipGetLastError(), fn);
-        }
-        if (LZQ_ODE_RICSEG && n > 1) {  // uniform 32/16/8-lane segments (a one-point wave is one whole segment)
-          if (rc != LZQ_OK) return rc;
-          hipLaunchKernelGGL((lzq::ode_riccati_kernel<0, false, true>), dim3((unsigned)ode_blocks(n)),
-                             dim3(lzq::kOdeBlock), 0, s, d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status,
-                             lzq::g_ode_coop, k_lo, k_cnt, st, d_skip);
-          rc = hip_check(hipGetLastError(), fn);
-          if (rc != LZQ_OK) return rc;
-          hipLaunchKernelGGL((lzq::ode_riccati_kernel<1, false, true>), dim3((unsigned)ode_blocks(n)),
-                             dim3(lzq::kOdeBlock), 0, s, d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status,
-                             lzq::g_ode_coop, k_lo, k_cnt, st, d_skip);
-          rc = hip_check(hipGetLastError(), fn);
-          if (rc != LZQ_OK) return rc;
-          hipLaunchKernelGGL((lzq::ode_riccati_kernel<2, false, true>), dim3((unsigned)ode_blocks(n)),
-                             dim3(lzq::kOdeBlock), 0, s, d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status,
-                             lzq::g_ode_coop, k_lo, k_cnt, st, d_skip);
-          rc = hip_check(hipGetLastError(), fn);
-        }
+      }
+      if (n > 1) {  // uniform 32/16/8-lane segments (a one-point wave is one whole segment)
+        if (rc != LZQ_OK) return rc;
+        hipLaunchKernelGGL((lzq::ode_riccati_kernel<0, false, true>), dim3((unsigned)ode_blocks(n)),
+                           dim3(lzq::kOdeBlock), 0, s, d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status,
+                           lzq::g_ode_coop, k_lo, k_cnt, st, d_skip);
+        rc = hip_check(hipGetLastError(), fn);
+        if (rc != LZQ_OK) return rc;
+        hipLaunchKernelGGL((lzq::ode_riccati_kernel<1, false, true>), dim3((unsigned)ode_blocks(n)),
+                           dim3(lzq::kOdeBlock), 0, s, d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status,
+                           lzq::g_ode_coop, k_lo, k_cnt, st, d_skip);
+        rc = hip_check(hipGetLastError(), fn);
+        if (rc != LZQ_OK) return rc;
+        hipLaunchKernelGGL((lzq::ode_riccati_kernel<2, false, true>), dim3((unsigned)ode_blocks(n)),
+                           dim3(lzq::kOdeBlock), 0, s, d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status,
+                           lzq::g_ode_coop, k_lo, k_cnt, st, d_skip);
+        rc = hip_check(hipGetLastError(), fn);
       }
     }
-    if constexpr (LZQ_ODE_LINFAST && LZQ_ODE_YBREC && !kChiOnly) {
+    if constexpr (!kChiOnly) {
       if (rc != LZQ_OK) return rc;
       hipLaunchKernelGGL((lzq::ode_integrate_kernel<kChiOnly, true>), dim3((unsigned)ode_blocks(n)),
                          dim3(lzq::kOdeBlock), 0, s, d_points, d_ode, n, d_tidx, d_work, max_steps, d_out, d_status,
@@ -1884,7 +1797,7 @@ int launch_integrate(const lzq_point* d_points, const lzq_ode_params* d_ode, int
   };
   // one launch needs no carried state, unless the Riccati passes (ode_riccati_kernel) hand a
   // wave's state from pass to pass
-  if (launches == 1 && !(LZQ_ODE_RICVAR && !kChiOnly)) return launch(0, 0, nullptr);
+  if (launches == 1 && kChiOnly) return launch(0, 0, nullptr);
   lzq::OdeState* st = nullptr;
   int rc = hip_check(hipMallocAsync((void**)&st, sizeof(lzq::OdeState) * (size_t)n, s), fn);
   if (rc) return rc;

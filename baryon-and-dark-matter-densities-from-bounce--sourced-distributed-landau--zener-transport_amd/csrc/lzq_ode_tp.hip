@@ -4,6 +4,20 @@
 // helpers (stages, Radau step, predictor) are lzq_ode.h's, shared with the sequential kernels.
 #include "lzq_ode.h"
 
+// Build switches of this file (lzq_ode.h's parameter table covers the shared ones):
+//
+// | name              | values | what it sets                                                        |
+// |-------------------|--------|---------------------------------------------------------------------|
+// | LZQ_ODE_TP_FUSE   | 1, 0   | a Newton update in two launches (1) or four (0); same operations     |
+// | LZQ_ODE_TP_DEBUG  | unset  | defined: debug prints of the iteration (tools/debug_ode_tp.py)       |
+//
+// LZQ_ODE_TP_FUSE is settled at 1 (round 6) and stays a switch only because the four-launch path
+// owns three kernels (ode_tp_interval_kernel, ode_tp_scan_local_kernel, ode_tp_scan_finish_kernel):
+// folding it would take them out of the code object.
+#ifndef LZQ_ODE_TP_FUSE
+#define LZQ_ODE_TP_FUSE 1
+#endif
+
 namespace lzq {
 
 // ---------------------------------------------------------------------------------------
@@ -167,12 +181,6 @@ struct TpRow {
   double lam[3], E2[3], S[3], c, d;
 };
 constexpr size_t kTpRowBytes = size_t(1) << 31;  // row tables of one call, at most (else stages inline)
-#ifndef LZQ_ODE_TP_FUSE
-#define LZQ_ODE_TP_FUSE 1  // a Newton update in two launches instead of four (same operations)
-#endif
-#ifndef LZQ_ODE_TP_ROWS
-#define LZQ_ODE_TP_ROWS 1  // 0: every step forms its stages inline (the round-5 path; same bits)
-#endif
 
 __global__ __launch_bounds__(256) void ode_tp_rows_kernel(const lzq_point* __restrict__ pts,
                                                           const lzq_ode_params* __restrict__ ode, int64_t n,
@@ -218,7 +226,7 @@ __device__ __forceinline__ bool tp_steps(const OdePoint& o, const double* __rest
                                          double& C, const TpRow* __restrict__ rows = nullptr, int64_t stride = 0) {
   const Radau R = radau_tableau();
   const RadauH hA = radau_h(R, h);
-  const bool riccati = LZQ_ODE_PREDICT && o.sigmav != 0.0;
+  const bool riccati = o.sigmav != 0.0;
   double Ychi = St.Ychi, YB = St.YB, Yp = St.Yp;
   double Zs[3] = {St.Z[0], St.Z[1], St.Z[2]};
   bool have = St.have, exact = true;
@@ -975,7 +983,7 @@ int launch_integrate_tp(const lzq_point* d_points, const lzq_ode_params* d_ode, 
   const size_t b_gd = up(sizeof(int32_t) * (size_t)n), b_gy = up(sizeof(double) * (size_t)n);
   // the regular steps' stage rows (TpRow), when the tables of the call fit kTpRowBytes
   const size_t rows_raw = sizeof(lzq::TpRow) * (size_t)n * (size_t)Mmax * (size_t)L;
-  const bool use_rows = LZQ_ODE_TP_ROWS && rows_raw <= lzq::kTpRowBytes;
+  const bool use_rows = rows_raw <= lzq::kTpRowBytes;
   const size_t b_rows = use_rows ? up(rows_raw) : 0;
   const size_t b_tk = up(sizeof(int32_t) * (size_t)n);
   char* buf = nullptr;

@@ -55,21 +55,29 @@
 
 int lzq_set_error(int code, const char* msg);
 
-namespace lzq {
-
-constexpr int kProfBlock = 256;
+// ---------------------------------------------------------------------------------------
+// Build parameters of this file (every settled on/off choice is plain code).
+//
+// | name               | values   | what it sets                                                  | measured                                  |
+// |--------------------|----------|---------------------------------------------------------------|-------------------------------------------|
+// | LZQ_PROF_MIN_WAVES | 2 (5, 6) | profile kernels: waves/SIMD floor (VGPR cap 512 / n)          | profiles/round6/ablate_profile_key.json   |
+// | LZQ_PROF_KEY_BINS  | 6        | launch-order key: cost bins per octave of a point's steps     | tools/profile_order_model.py              |
+// | LZQ_PROF_PAIR      | 0, 1     | 1: the interval loop's Magnus steps two per iteration (state  | profiles/round6/ablate_profile_key.json   |
+// |                    |          | in alternating registers); slower, kept for tools/ablate_profile.py |                                     |
+// ---------------------------------------------------------------------------------------
 #ifndef LZQ_PROF_MIN_WAVES
 #define LZQ_PROF_MIN_WAVES 2
 #endif
+#ifndef LZQ_PROF_KEY_BINS
+#define LZQ_PROF_KEY_BINS 6
+#endif
 #ifndef LZQ_PROF_PAIR
-#define LZQ_PROF_PAIR 0  // the interval loop's Magnus steps two per iteration (state in alternating registers)
+#define LZQ_PROF_PAIR 0
 #endif
-#ifndef LZQ_PROF_UNIFORM
-#define LZQ_PROF_UNIFORM 1  // waves whose points share one shape read its rows through the scalar cache
-#endif
-#ifndef LZQ_PROF_SORT
-#define LZQ_PROF_SORT 1  // keyed launch order for batches of >= kProfSortMin points (0: index order)
-#endif
+
+namespace lzq {
+
+constexpr int kProfBlock = 256;
 constexpr int64_t kProfSortMin = 16384;
 constexpr int kProfCostStride = 16;  // the launch-order cost model samples every 16th knot interval
 constexpr double kMaxIntervalSteps = 16777216.0;  // per knot interval; beyond: P = NaN (absurd input)
@@ -509,11 +517,7 @@ __device__ __forceinline__ Rates sample_rates(const double* __restrict__ sr, con
 // it cannot prove canonical (a v_max_f64 x, x for each carried or loaded value, three per interval
 // entry); the rule's operands are never signalling NaNs, and for every other input v_max_f64 is
 // fmax (a quiet NaN operand yields the other).
-#ifndef LZQ_PROF_ASM_MAX
-#define LZQ_PROF_ASM_MAX 1
-#endif
 __device__ __forceinline__ double rmax(double a, double b) {
-  if (!LZQ_PROF_ASM_MAX) return fmax(a, b);
   double r;
   asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
@@ -541,23 +545,16 @@ __device__ __forceinline__ Rates interval_rates(const double* __restrict__ sm, i
 // refinements, wrapped in range fix-ups (a 2^256 pre-scale below 2^-767, 0 / +inf passed through).
 // When every lane's argument lies in [2^-767, DBL_MAX] the fix-ups are identities, so the bare
 // sequence gives the library's bits; otherwise the wave takes the library sqrt.
-#ifndef LZQ_PROF_RULE_SQRT
-#define LZQ_PROF_RULE_SQRT 1
-#endif
 // every active lane's x in [2^-767, DBL_MAX] (NaN: no): the two compares' lane masks straight into
 // SGPRs (a ballot of the C++ condition re-materialises it as a VGPR and compares that again)
-#ifndef LZQ_PROF_VOTE_ASM
-#define LZQ_PROF_VOTE_ASM 1
-#endif
 __device__ __forceinline__ bool wave_in_sqrt_range(double x) {
-  if (!LZQ_PROF_VOTE_ASM) return __all(x >= 0x1p-767 && x <= 0x1.fffffffffffffp+1023);
   uint64_t lo, hi;
   asm("v_cmp_le_f64_e64 %0, %1, %2" : "=s"(lo) : "s"(0x1p-767), "v"(x));
   asm("v_cmp_ge_f64_e64 %0, %1, %2" : "=s"(hi) : "s"(0x1.fffffffffffffp+1023), "v"(x));
   return (lo & hi) == __builtin_amdgcn_read_exec();
 }
 __device__ __forceinline__ double rule_sqrt(double x) {
-  if (LZQ_PROF_RULE_SQRT && wave_in_sqrt_range(x)) {
+  if (wave_in_sqrt_range(x)) {
     const double y = __builtin_amdgcn_rsq(x);
     double g = x * y, h = y * 0.5;
     const double r = __builtin_fma(-h, g, 0.5);
@@ -602,12 +599,6 @@ __device__ __forceinline__ double interval_steps(const double* __restrict__ sm, 
 // next (boustrophedon), so a wave that straddles two cost bins holds neighbouring angles, not
 // the two ends of the range: the model's 1.131 -> 1.102 (tools/profile_order_model.py).
 constexpr int kAngleBins = 256;
-#ifndef LZQ_PROF_KEY_SERP
-#define LZQ_PROF_KEY_SERP 1
-#endif
-#ifndef LZQ_PROF_KEY_BINS
-#define LZQ_PROF_KEY_BINS 6
-#endif
 constexpr double kKeyBinsPerOctave = LZQ_PROF_KEY_BINS;  // 128 bins: saturate at 2^21 steps per point
 __global__ __launch_bounds__(kProfBlock) void profile_key_kernel(const double* __restrict__ knots, int32_t n_shapes,
                                                                  int32_t K, const lzq_profile_point* __restrict__ pts,
@@ -627,15 +618,15 @@ __global__ __launch_bounds__(kProfBlock) void profile_key_kernel(const double* _
       return c * kProfCostStride;
     };
     const int64_t s0 = __builtin_amdgcn_readfirstlane(p.shape), sl = p.shape;  // scalar loads when uniform
-    st = (LZQ_PROF_UNIFORM && __all(p.shape == s0)) ? cost(knots + s0 * K, samp + s0 * (K - 1) * kProfRec)
-                                                    : cost(knots + sl * K, samp + sl * (K - 1) * kProfRec);
+    st = __all(p.shape == s0) ? cost(knots + s0 * K, samp + s0 * (K - 1) * kProfRec)
+                              : cost(knots + sl * K, samp + sl * (K - 1) * kProfRec);
   }
   const double cb = st == st ? fmin(fmax(kKeyBinsPerOctave * log2(1.0 + st), 0.0), (double)(kCostBins - 1)) : 0.0;
   const uint32_t cost = (uint32_t)((kCostBins - 1) - (int32_t)cb);  // 0 = costliest
   const double ang = atan(p.ychi / p.yB);                            // (-pi/2, pi/2); NaN for 0/0
   const double af = ang == ang ? (ang * (1.0 / 3.141592653589793) + 0.5) * kAngleBins : 0.0;
   uint32_t ab = (uint32_t)fmin(fmax(af, 0.0), (double)(kAngleBins - 1));
-  if (LZQ_PROF_KEY_SERP && (cost & 1)) ab = (kAngleBins - 1) - ab;  // boustrophedon: see kKeyBinsPerOctave
+  if (cost & 1) ab = (kAngleBins - 1) - ab;  // boustrophedon: see kKeyBinsPerOctave
   const uint32_t sh = valid ? (uint32_t)min(p.shape, 65534) : (uint32_t)min(n_shapes, 65535);  // invalid: last
   keys[i] = (sh << 15) | (cost << 8) | ab;  // shape, 7 + 8 bits
   idx[i] = (int32_t)i;
@@ -747,9 +738,6 @@ __device__ __forceinline__ double propagate_point(const double* __restrict__ rec
   return 1.0 - (a.re * a.re + a.im * a.im) / norm;
 }
 
-#ifndef LZQ_PROF_STAGE
-#define LZQ_PROF_STAGE 1  // 0: every wave reads its spans from global memory
-#endif
 
 // The interval loop walks every lane of a wave through the same knot interval j, so when the wave's
 // points share one shape (the keyed launch order makes that the rule) the interval's records are
@@ -770,7 +758,7 @@ __global__ __launch_bounds__(kProfBlock, LZQ_PROF_MIN_WAVES) void profile_propag
   }
   const int32_t sh0 = __builtin_amdgcn_readfirstlane(p.shape);
   double P;
-  if (LZQ_PROF_STAGE && __builtin_amdgcn_read_exec() == ~0ull && __all(p.shape == sh0)) {
+  if (__builtin_amdgcn_read_exec() == ~0ull && __all(p.shape == sh0)) {
     P = propagate_point<true>(rec + (int64_t)sh0 * (K - 1) * kProfRec, K, p, spr, n_min, &stage[threadIdx.x >> 6]);
   } else {
     P = propagate_point<false>(rec + (int64_t)p.shape * (K - 1) * kProfRec, K, p, spr, n_min, nullptr);
@@ -929,7 +917,7 @@ int profile_flat_launch(const double* d_knots, const double* d_coef, int32_t n_s
   for (int64_t s0 = 0; s0 < n && rc == LZQ_OK && e == hipSuccess; s0 += per) {
     const int64_t m = std::min(per, n - s0);
     const int64_t nb = (m + lzq::kProfBlock - 1) / lzq::kProfBlock;
-    const bool sort = LZQ_PROF_SORT && m >= lzq::kProfSortMin;
+    const bool sort = m >= lzq::kProfSortMin;
     if (sort) e = hipMemsetAsync(hist, 0, sizeof(int32_t) * lzq::kCostBins, st);
     if (e != hipSuccess) break;
     hipLaunchKernelGGL(lzq::profile_steps_kernel, dim3((unsigned)nb), dim3(lzq::kProfBlock), 0, st, d_knots, n_shapes, K,
@@ -1014,7 +1002,7 @@ extern "C" int lzq_lz_propagate_profile(const double* d_knots, const double* d_c
   char* ws = nullptr;
   const int32_t* order = nullptr;
   int rc = LZQ_OK;
-  if (LZQ_PROF_SORT && n >= lzq::kProfSortMin) {
+  if (n >= lzq::kProfSortMin) {
     size_t tmp_bytes = 0;
     // sort only the key bits in use: the shape field needs bits for n_shapes + 1 values (invalid last)
     int end_bit = 15;

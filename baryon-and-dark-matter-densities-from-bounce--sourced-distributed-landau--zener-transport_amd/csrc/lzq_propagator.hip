@@ -62,21 +62,29 @@
 #include "lzq_su2.h"
 #include "lzq_superadiabatic.h"
 
+// ---------------------------------------------------------------------------------------
+// Build parameters of this file (numeric; every settled on/off choice is plain code).
+// lzq_superadiabatic.h adds LZQ_SA_PHASE_UNROLL and LZQ_FOLLOW_JOB_UNROLL.
+//
+// | name                 | default | what it sets                                | measured                                   |
+// |----------------------|---------|---------------------------------------------|--------------------------------------------|
+// | LZQ_PROP_UNROLL      | 3       | lz_propagate_kernel's step-loop unroll      | 1 -> 3: -12%, profiles/round3/ablate_prop_unroll_r3.json |
+// | LZQ_PROP_MIN_WAVES   | 2       | lz_propagate_kernel: waves/SIMD floor       | 2: 217 VGPRs, no spills; 3: 168 with spills, same time   |
+// | LZQ_FOLLOW_MIN_WAVES | 1       | lz_follow_kernel: waves/SIMD floor          | tools/ablate_prop.py, DESIGN §4.4          |
+// ---------------------------------------------------------------------------------------
+#ifndef LZQ_PROP_UNROLL
+#define LZQ_PROP_UNROLL 3
+#endif
+#ifndef LZQ_PROP_MIN_WAVES
+#define LZQ_PROP_MIN_WAVES 2
+#endif
+#ifndef LZQ_FOLLOW_MIN_WAVES
+#define LZQ_FOLLOW_MIN_WAVES 1
+#endif
+
 namespace lzq {
 
 constexpr int kPropBlock = 256;
-#ifndef LZQ_PROP_UNROLL
-#define LZQ_PROP_UNROLL 3  // step-loop unroll: ILP across steps (A/B: 1 -> 3 = -12%, tools/ablate_prop.py)
-#endif
-#ifndef LZQ_PROP_MIN_WAVES
-#define LZQ_PROP_MIN_WAVES 2  // 217 VGPRs with the 3-step unroll, no spills (3 waves/SIMD: 168 VGPRs, spills; same time)
-#endif
-#ifndef LZQ_FOLLOW_SPLIT
-#define LZQ_FOLLOW_SPLIT 0  // 1: lz_follow_split_kernel (three frame jobs on three wavefronts; measured slower)
-#endif
-#ifndef LZQ_FOLLOW_MIN_WAVES
-#define LZQ_FOLLOW_MIN_WAVES 1  // lz_follow_kernel's occupancy floor (tools/ablate_prop.py)
-#endif
 constexpr double kDeltaAdiabatic = 16.0;              // e^{-2 pi 16} = 2e-44
 constexpr double kStepsPerRadian = 6.0;              // Magnus steps per radian of adiabatic phase in a core
 constexpr double kMaxCellSteps = 16777216.0;         // per-cell Magnus steps beyond this: P = NaN (bad input)
@@ -125,17 +133,8 @@ __device__ __forceinline__ void chi_like_dressed(double d, double ddot, double m
   u1 = plus ? b.p1 : b.q1;
 }
 
-#ifndef LZQ_PROP_POLY
-#define LZQ_PROP_POLY 1  // 0: the Magnus vector from D and E^2 per step (round 3; tools/ablate_prop.py)
-#endif
-
-#ifndef LZQ_PROP_CORE
-#define LZQ_PROP_CORE 1  // 0: Magnus over every whole cell (round-1 scheme; tools/ablate_prop.py)
-#endif
-
 // Core of a delta <= 16 cell in xi: [xc - W, xc + W], W = tau_c v_w / sqrt(alpha)
 __device__ __forceinline__ double core_halfwidth(double m, double a, double v_w) {
-  if (!LZQ_PROP_CORE) return INFINITY;
   const double sa = sqrt(a * v_w);
   return sa_core_tau(m / sa) * v_w / sa;
 }
@@ -151,9 +150,6 @@ __device__ __forceinline__ double core_halfwidth(double m, double a, double v_w)
 // computed by one lane from its own inputs, so P is bit-identical to index order; only the
 // order within a bin depends on the scatter's atomics.
 // ---------------------------------------------------------------------------------------
-#ifndef LZQ_PROP_SORT
-#define LZQ_PROP_SORT 1  // 0: index order (tools/ablate_prop.py)
-#endif
 constexpr int64_t kSortMinPoints = 16384;  // below this the three extra launches do not pay
 
 constexpr int kFollowDoubles = 11;  // per (point, cell): two SU(2) matrices, the core's edges, its steps
@@ -280,7 +276,7 @@ __global__ __launch_bounds__(kPropBlock, LZQ_FOLLOW_MIN_WAVES) void lz_follow_ke
     out[10] = -1.0;
     return;
   }
-  const double W = core_halfwidth(mc, ac, v_w);  // INFINITY without cores (LZQ_PROP_CORE=0)
+  const double W = core_halfwidth(mc, ac, v_w);
   const double cl = fmax(left, xcc - W), cr = fmin(right, xcc + W);
   const double Phic = (wkb_G(ac * (cr - xcc), mc) - wkb_G(ac * (cl - xcc), mc)) / (ac * v_w);
   const double Sd = fmax((double)S, ceil(Phic * kStepsPerRadian));
@@ -292,111 +288,6 @@ __global__ __launch_bounds__(kPropBlock, LZQ_FOLLOW_MIN_WAVES) void lz_follow_ke
   out[10] = Sd <= kMaxCellSteps ? Sd : __builtin_nan("");  // non-finite or absurd input: P = NaN
   const bool has_left = left < cl, has_right = cr < right;
   sa_cell_follow(mh, sg, sa * (left - xcc) * inv_vw, sa * (right - xcc) * inv_vw, tau_c, has_left, has_right, out);
-}
-
-// lz_follow_kernel with a cell's three frame jobs on three wavefronts (round 6, LZQ_FOLLOW_SPLIT):
-// a block takes 64 cells; wave 0 forms each cell's core-edge frame U(tau_c) (and the header:
-// edges, step count, or the closed form of an adiabatic cell), wave 1 the left stretch's outer
-// frame and phase, wave 2 the right one's; after a block barrier waves 1 and 2 combine them with
-// the core frame from LDS and store ML / MR.  sa_cell_follow's operations per job, so the same
-// matrices; what changes is that a lane carries one frame chain at a time instead of three
-// (its registers: more waves per SIMD to hide the chains' latency) and a wave runs one kind of
-// job (no has_left / has_right predication across the three).
-constexpr int kFollowCells = 64;
-#ifndef LZQ_FOLLOW_SPLIT_WAVES
-#define LZQ_FOLLOW_SPLIT_WAVES 4  // lz_follow_split_kernel's waves per SIMD (its VGPR cap = 512 / this)
-#endif
-__global__ __launch_bounds__(3 * kFollowCells) __attribute__((amdgpu_waves_per_eu(LZQ_FOLLOW_SPLIT_WAVES)))
-void lz_follow_split_kernel(
-    const double* __restrict__ m_mix, const double* __restrict__ dprime, const double* __restrict__ xi,
-    const double* __restrict__ vw, int64_t n, int32_t n_cross, double v_w0, double K, int32_t S,
-    double* __restrict__ follow) {
-  struct Geo {
-    double tl, tr, tau_c, mh;
-    int32_t sides;  // bit 0: the left stretch, bit 1: the right one
-  };
-  __shared__ SU2 s_uc[kFollowCells];
-  __shared__ Geo s_geo[kFollowCells];
-  const int lane = threadIdx.x & 63, job = threadIdx.x >> 6;  // job: wave-uniform
-  const int64_t t = (int64_t)blockIdx.x * kFollowCells + lane;
-  const int c = t < n * n_cross ? (int)(t % n_cross) : 0;
-  const double sg = (c % 2 == 0) ? 1.0 : -1.0;
-  double* out = follow + t * kFollowDoubles;
-  if (job == 0) {  // the cell's geometry (lz_follow_kernel's, verbatim), the header and the core frame
-    Geo geo{0.0, 0.0, 0.0, 0.0, 0};
-    const int64_t p = t / n_cross;
-    const double v_w = t < n * n_cross ? (vw ? vw[p] : v_w0) : 0.0;
-    if (t < n * n_cross && v_w > 0.0) {  // (the propagate kernel writes NaN for a bad wall speed)
-      const double* mm = m_mix + p * n_cross;
-      const double* dp = dprime + p * n_cross;
-      const double* xc = xi + p * n_cross;
-      const double ac = fabs(dp[c]), mc = mm[c], xcc = xc[c];
-      double left, right;
-      if (c == 0) {
-        left = xc[0] - K * lz_length(mm[0], fabs(dp[0]), v_w);
-      } else {
-        const double ap = fabs(dp[c - 1]);
-        left = (ap * xc[c - 1] + ac * xcc) / (ap + ac);
-      }
-      if (c + 1 < n_cross) {
-        const double an = fabs(dp[c + 1]);
-        right = (ac * xcc + an * xc[c + 1]) / (ac + an);
-      } else {
-        right = xcc + K * lz_length(mc, ac, v_w);
-      }
-      const double delta = mc * mc / (2.0 * v_w * ac);
-      if (delta > kDeltaAdiabatic) {
-        const double slope = sg * ac;
-        const double Phi = (wkb_G(ac * (right - xcc), mc) - wkb_G(ac * (left - xcc), mc)) / (ac * v_w);
-        const double DL = slope * (left - xcc), DR = slope * (right - xcc);
-        const double ddot = slope * v_w;
-        const Dressed L = dressed_basis(DL, ddot, mc), R = dressed_basis(DR, ddot, mc);
-        const double id = 1.0 / delta, id2 = id * id;
-        const double phiS = id * (1.0 / 12.0 + id2 * (1.0 / 360.0 + id2 * (1.0 / 1260.0 + id2 * (1.0 / 1680.0))));
-        const double tails = 0.125 * mc * mc * ac * v_w * (tail_T(DL, mc) + tail_T(DR, mc));
-        const SU2 m = su2_mul({R.p0, R.p1}, su2_phase_adj(Phi + phiS - tails, {L.p0, L.p1}));
-        out[0] = m.a.re, out[1] = m.a.im, out[2] = m.b.re, out[3] = m.b.im;
-        out[10] = -1.0;
-      } else {
-        const double W = core_halfwidth(mc, ac, v_w);
-        const double cl = fmax(left, xcc - W), cr = fmin(right, xcc + W);
-        const double Phic = (wkb_G(ac * (cr - xcc), mc) - wkb_G(ac * (cl - xcc), mc)) / (ac * v_w);
-        const double Sd = fmax((double)S, ceil(Phic * kStepsPerRadian));
-        const double inv_vw = 1.0 / v_w;
-        const double sa = sqrt(ac * v_w);
-        geo.mh = mc / sa;
-        geo.tau_c = W * sa * inv_vw;
-        geo.tl = sa * (left - xcc) * inv_vw;
-        geo.tr = sa * (right - xcc) * inv_vw;
-        geo.sides = (left < cl ? 1 : 0) | (cr < right ? 2 : 0);
-        out[8] = cl;
-        out[9] = cr;
-        out[10] = Sd <= kMaxCellSteps ? Sd : __builtin_nan("");
-      }
-    }
-    s_geo[lane] = geo;
-  }
-  __syncthreads();
-  const Geo geo = s_geo[lane];
-  // wave 0: the core frame; waves 1, 2: the outer frame and the phase of their stretch
-  const bool mine = job == 0 ? geo.sides != 0 : ((geo.sides >> (job - 1)) & 1) != 0;
-  SU2 u{};
-  double ph = 0.0;
-  if (mine) {
-    if (job == 0) {
-      s_uc[lane] = sa_frame(geo.tau_c, sg, geo.mh, false);
-    } else {
-      const double tau = job == 1 ? geo.tl : geo.tr;
-      u = sa_frame(tau, sg, geo.mh, true);
-      ph = job == 1 ? sa_phase(geo.tl, -geo.tau_c, geo.mh) : sa_phase(geo.tau_c, geo.tr, geo.mh);
-    }
-  }
-  __syncthreads();
-  if (mine && job > 0) {
-    const SU2 uc = s_uc[lane];
-    if (job == 1) sa_store(su2_mul(sa_reflect(uc), su2_phase_adj(ph, u)), out);  // U(-tau_c) P U(tl)^+
-    else sa_store(su2_mul(u, su2_phase_adj(ph, uc)), out + 4);                   // U(tr) P U(tau_c)^+
-  }
 }
 
 __global__ __launch_bounds__(kPropBlock, LZQ_PROP_MIN_WAVES) void lz_propagate_kernel(const double* __restrict__ m_mix,
@@ -468,7 +359,6 @@ __global__ __launch_bounds__(kPropBlock, LZQ_PROP_MIN_WAVES) void lz_propagate_k
       // oracle-matching kernels, so contraction is spelled out): 63 VALU per step where the
       // separate products and sums took 84.
 #define FMA __builtin_fma
-#if LZQ_PROP_POLY
       // Round 4: n as polynomials in the step's midpoint D = D0 + i dD (D linear in xi):
       //   n_x = kx0 + kx2 D^2,  n_y = ky0 + ky2 D^2 + ky4 D^4,  n_z = cz D
       // (the header's coefficients expanded in E^2 = D^2 + m^2 once per cell), 7 VALU for the
@@ -487,19 +377,6 @@ __global__ __launch_bounds__(kPropBlock, LZQ_PROP_MIN_WAVES) void lz_propagate_k
         cos_sinc_short(FMA(nx, nx, FMA(ny, ny, nz * nz)), cs, sc);
         su2_apply(cs, sc * nx, sc * ny, sc * nz, p0, p1);
       };
-#else
-      auto step = [&](int i) {
-        const double xm = FMA((double)i + 0.5, h, cl);
-        const double D = slope * (xm - xcc);
-        const double D2 = D * D, E2 = D2 + m2;
-        const double nx = cxm * FMA(-bx, FMA(3.0, D2, m2x4), ax);
-        const double ny = cy * FMA(ey2, FMA(8.0 * E2, E2, -dd2x9), FMA(ey1, E2, 1.0 / 6.0));
-        const double nz = cz * D;
-        double cs, sc;  // cos|n| and sin|n|/|n|, both functions of |n|^2
-        cos_sinc(FMA(nx, nx, FMA(ny, ny, nz * nz)), cs, sc);
-        su2_apply(cs, sc * nx, sc * ny, sc * nz, p0, p1);
-      };
-#endif
       // unrolled by hand: the polynomial's inline asm (fma3) is convergent, which rules out
       // the compiler's runtime unrolling
       int i = 0;
@@ -541,7 +418,7 @@ int propagate_slice(const double* d_m_mix, const double* d_dprime, const double*
   const int64_t nb = (n + lzq::kPropBlock - 1) / lzq::kPropBlock;
   // stream-ordered scratch (calls on different streams stay independent): the follow matrices,
   // then the longest-first launch order (see lz_cost_kernel) for large batches
-  const bool sort = LZQ_PROP_SORT && n >= lzq::kSortMinPoints;
+  const bool sort = n >= lzq::kSortMinPoints;
   const size_t follow_bytes = (size_t)(n * n_cross) * lzq::kFollowDoubles * sizeof(double);
   const size_t sort_bytes = sort ? (size_t)(2 * n + 2 * lzq::kCostBins) * sizeof(int32_t) : 0;
   char* ws = nullptr;
@@ -553,15 +430,9 @@ int propagate_slice(const double* d_m_mix, const double* d_dprime, const double*
   const int32_t* order = nullptr;
   hipError_t e = hipSuccess;
   {
-    if (LZQ_FOLLOW_SPLIT) {
-      const int64_t nf = (n * n_cross + lzq::kFollowCells - 1) / lzq::kFollowCells;
-      hipLaunchKernelGGL(lzq::lz_follow_split_kernel, dim3((unsigned)nf), dim3(3 * lzq::kFollowCells), 0, st, d_m_mix,
-                         d_dprime, d_xi, d_v_w, n, n_cross, v_w, window_lz, steps_per_crossing, follow);
-    } else {
-      const int64_t nf = (n * n_cross + lzq::kPropBlock - 1) / lzq::kPropBlock;
-      hipLaunchKernelGGL(lzq::lz_follow_kernel, dim3((unsigned)nf), dim3(lzq::kPropBlock), 0, st, d_m_mix, d_dprime,
-                         d_xi, d_v_w, n, n_cross, v_w, window_lz, steps_per_crossing, follow);
-    }
+    const int64_t nf = (n * n_cross + lzq::kPropBlock - 1) / lzq::kPropBlock;
+    hipLaunchKernelGGL(lzq::lz_follow_kernel, dim3((unsigned)nf), dim3(lzq::kPropBlock), 0, st, d_m_mix, d_dprime,
+                       d_xi, d_v_w, n, n_cross, v_w, window_lz, steps_per_crossing, follow);
   }
   if (sort) {
     int32_t* iw = (int32_t*)(ws + follow_bytes);

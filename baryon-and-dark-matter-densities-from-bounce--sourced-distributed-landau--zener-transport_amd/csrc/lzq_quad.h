@@ -89,6 +89,11 @@ constexpr int kWavesPerBlock = kBlock / kWaveSize;
 #ifndef LZQ_MIN_WAVES
 #define LZQ_MIN_WAVES 8
 #endif
+// the same for the table-reuse kernels (grid_reuse, points_reuse, their window forms and grid_solve):
+// 8 waves/SIMD (SGPRs capped, a few spilled to VGPR lanes): +12% over 7 (tools/ablate_builds.py ... reuse)
+#ifndef LZQ_REUSE_MIN_WAVES
+#define LZQ_REUSE_MIN_WAVES 8
+#endif
 constexpr int kKUnroll = LZQ_KUNROLL;  // z-nodes per scalar-load batch (must divide 1200)
 constexpr int kYB = LZQ_YB;            // y-nodes per lane per pass (independent chains)
 static_assert(kNZ % kKUnroll == 0, "z unroll must divide nz");

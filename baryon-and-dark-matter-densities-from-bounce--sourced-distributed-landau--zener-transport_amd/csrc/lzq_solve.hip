@@ -64,10 +64,6 @@ __device__ __forceinline__ SolveState load_state(const SolveState& m) {
   return s;
 }
 
-#ifndef LZQ_REUSE_MIN_WAVES
-#define LZQ_REUSE_MIN_WAVES 8
-#endif
-
 // WIN: the window of the point's block (SlotWindow), else the point's Gaussian (SlotGaussWindow)
 template <bool WIN>
 __global__ __launch_bounds__(kBlock, LZQ_REUSE_MIN_WAVES) void grid_solve_kernel(

@@ -28,11 +28,7 @@ static __constant__ double kCosC[10] = {0x1.0000000000000p+0,  -0x1.000000000000
 // Three-address FP64 fma.  The Horner steps below add a loop-invariant coefficient; written as
 // __builtin_fma the compiler picks the two-address v_fmac_f64 and copies the coefficient into the
 // accumulator first (one v_mov_b64 per term, ~19 per Magnus step); v_fma_f64 needs no copy.
-#ifndef LZQ_SU2_FMA3
-#define LZQ_SU2_FMA3 1  // 0: __builtin_fma (tools/ablate_prop.py)
-#endif
 __device__ __forceinline__ double fma3(double a, double b, double c) {
-  if (!LZQ_SU2_FMA3) return __builtin_fma(a, b, c);
   double r;
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
   return r;
@@ -42,7 +38,6 @@ __device__ __forceinline__ double fma3(double a, double b, double c) {
 // one scalar operand for free, so the constants need neither VGPRs nor the per-step v_mov copies the
 // register allocator otherwise inserts to rebuild them (round 4: ~17 VALU per profile Magnus step).
 __device__ __forceinline__ double fma3s(double a, double b, double c) {
-  if (!LZQ_SU2_FMA3) return __builtin_fma(a, b, c);
   double r;
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c));
   return r;
@@ -68,14 +63,8 @@ __device__ __forceinline__ void cos_sinc(double x2, double& cs, double& sc) {
 // The same for |n|^2 <= 1/4 with the Taylor series cut at 7 (sinc) and 8 (cos) terms (< 1e-16
 // there), and at 7 + 7 for |n|^2 <= 1/8 (< 6e-18); both propagators step at >= 3 steps per
 // radian, where |n|^2 <~ 0.12.  Beyond 1/4 the full series (and sincos beyond 1).
-#ifndef LZQ_SU2_SHORTSC
-#define LZQ_SU2_SHORTSC 1
-#endif
-#ifndef LZQ_SU2_SHORT8
-#define LZQ_SU2_SHORT8 1  // |n|^2 <= 1/8 (the usual step): 7 + 7 terms (< 6e-18)
-#endif
 __device__ __forceinline__ void cos_sinc_short(double x2, double& cs, double& sc) {
-  if (LZQ_SU2_SHORT8 && x2 <= 0.125) {
+  if (x2 <= 0.125) {
     double ps = kSincC[6], pc = kCosC[6];
 #pragma unroll
     for (int k = 5; k >= 0; --k) ps = fma3s(ps, x2, kSincC[k]);
@@ -83,7 +72,7 @@ __device__ __forceinline__ void cos_sinc_short(double x2, double& cs, double& sc
     for (int k = 5; k >= 0; --k) pc = fma3s(pc, x2, kCosC[k]);
     sc = ps;
     cs = pc;
-  } else if (LZQ_SU2_SHORTSC && x2 <= 0.25) {
+  } else if (x2 <= 0.25) {
     double ps = kSincC[6], pc = kCosC[7];
 #pragma unroll
     for (int k = 5; k >= 0; --k) ps = fma3s(ps, x2, kSincC[k]);
@@ -99,9 +88,6 @@ __device__ __forceinline__ void cos_sinc_short(double x2, double& cs, double& sc
 // cos|n| and sin|n|/|n| of a step (cos_sinc_short's values): the usual |n|^2 <= 1/8 inline, the
 // rest out of line, so the longer series' coefficients hold no registers in the step loops
 // (lzq_profile.hip's Magnus step, lzq_propagator.hip's core steps)
-#ifndef LZQ_SU2_COLD_SC
-#define LZQ_SU2_COLD_SC 1  // 0: cos_sinc_short inline (tools/ablate_profile.py, tools/ablate_prop.py)
-#endif
 struct CosSinc {
   double cs, sc;
 };
@@ -111,9 +97,7 @@ static __device__ __noinline__ CosSinc cos_sinc_cold(double x2) {
   return r;
 }
 __device__ __forceinline__ void cos_sinc_step(double x2, double& cs, double& sc) {
-  if (!LZQ_SU2_COLD_SC || !LZQ_SU2_SHORT8) {
-    cos_sinc_short(x2, cs, sc);
-  } else if (x2 <= 0.125) {
+  if (x2 <= 0.125) {
     double ps = kSincC[6], pc = kCosC[6];
 #pragma unroll
     for (int k = 5; k >= 0; --k) ps = fma3s(ps, x2, kSincC[k]);

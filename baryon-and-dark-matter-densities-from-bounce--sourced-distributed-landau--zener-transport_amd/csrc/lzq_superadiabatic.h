@@ -22,17 +22,25 @@
 
 #include "lzq_su2.h"
 
+// Build parameters of this header (numeric; every settled on/off choice is plain code):
+//
+// | name                  | default | what it sets                                                 | measured                       |
+// |-----------------------|---------|--------------------------------------------------------------|--------------------------------|
+// | LZQ_SA_PHASE_UNROLL   | 1       | sa_phase: its 4 Gauss points one after another (2, 4: side by side) | tools/ablate_prop.py    |
+// | LZQ_FOLLOW_JOB_UNROLL | 1       | sa_cell_follow: 3 = the three frames straight-line (342 VGPRs) | tools/ablate_follow.sh, DESIGN §7 |
+#ifndef LZQ_SA_PHASE_UNROLL
+#define LZQ_SA_PHASE_UNROLL 1
+#endif
+#ifndef LZQ_FOLLOW_JOB_UNROLL
+#define LZQ_FOLLOW_JOB_UNROLL 1
+#endif
+
 namespace lzq {
 
 // The frame and phase algebra below is checked against the numpy restatement at tolerances, not bit
 // for bit, so its products and sums may contract to fma (the library builds with -ffp-contract=off
 // for the oracle-matched quadrature); reset to off at the end of this header.
-#ifndef LZQ_SA_CONTRACT
-#define LZQ_SA_CONTRACT 1
-#endif
-#if LZQ_SA_CONTRACT
 #pragma clang fp contract(fast)
-#endif
 
 constexpr int kSALevels = 10;      // frame order outside a Magnus core (rotations V_0 .. V_9)
 constexpr double kSATol = 1e-11;   // core edge: first neglected angle |theta_10| <= this
@@ -44,11 +52,8 @@ constexpr double kSAFarC = 80.0;   //   |theta_6| <= kSAFarC mh / E^13 (fitted) 
 // from the range limits).  On the device v_rcp_f64 + two Newton steps (<= 1 ulp from the
 // quotient, ~4 VALU where the IEEE division takes ~10; the follow kernel divides ~130 times per
 // cell); the host build (tests/test_superadiabatic_host.py) divides.
-#ifndef LZQ_SA_FASTDIV
-#define LZQ_SA_FASTDIV 1
-#endif
 __host__ __device__ __forceinline__ double sa_rcp(double x) {
-#if defined(__HIP_DEVICE_COMPILE__) && LZQ_SA_FASTDIV
+#if defined(__HIP_DEVICE_COMPILE__)
   double r = __builtin_amdgcn_rcp(x);
   double e = __builtin_fma(-x, r, 1.0);
   r = __builtin_fma(r, e, r);
@@ -62,12 +67,9 @@ __host__ __device__ __forceinline__ double sa_rcp(double x) {
 // 1/sqrt(x) for the same quantities: v_rsq_f64 + two Newton steps r += r (1 - x r^2) / 2 (~1 ulp).
 // A square root and a reciprocal of the same number then cost one such chain (sqrt(x) = x rsqrt(x),
 // 1/x = rsqrt(x)^2) instead of the IEEE square root's refinement followed by sa_rcp's: the frame
-// levels are a dependent chain of these, so their latency is the follow kernel's (LZQ_SA_RSQRT).
-#ifndef LZQ_SA_RSQRT
-#define LZQ_SA_RSQRT 1
-#endif
+// levels are a dependent chain of these, so their latency is the follow kernel's.
 __host__ __device__ __forceinline__ double sa_rsqrt(double x) {
-#if defined(__HIP_DEVICE_COMPILE__) && LZQ_SA_FASTDIV
+#if defined(__HIP_DEVICE_COMPILE__)
   double r = __builtin_amdgcn_rsq(x);
   double e = __builtin_fma(-(x * r), r, 1.0);
   r = __builtin_fma(0.5 * r, e, r);
@@ -81,21 +83,11 @@ __host__ __device__ __forceinline__ double sa_rsqrt(double x) {
 // cos theta, sin theta from cos 2theta = c2, sin 2theta = s2 >= 0 (theta in [0, pi/2]) or any
 // s2 with c2 > 0, without cancellation
 __host__ __device__ __forceinline__ void half_angle(double c2, double s2, bool pos, double& c, double& s) {
-#if LZQ_SA_RSQRT
   const double x = 0.5 * (pos ? 1.0 + c2 : 1.0 - c2);  // in [1/2, 1]
   const double rr = sa_rsqrt(x);
   const double big = x * rr, small = s2 * (0.5 * rr);
   c = pos ? big : small;
   s = pos ? small : big;
-#else
-  if (pos) {
-    c = sqrt(0.5 * (1.0 + c2));
-    s = s2 * (0.5 * sa_rcp(c));
-  } else {
-    s = sqrt(0.5 * (1.0 - c2));
-    c = s2 * (0.5 * sa_rcp(s));
-  }
-#endif
 }
 
 // The frame rotation U = V_0 V_1 .. V_{N-1} accumulated as it is built: an SU(2) element
@@ -136,13 +128,8 @@ __host__ __device__ __forceinline__ void sa_chain(double (&e)[M], double (&g)[M]
       if (l % 2 == 0) acc = __builtin_fma(e[l / 2], e[l / 2], __builtin_fma(g[l / 2], g[l / 2], acc));
       q[l] = acc;
     }
-#if LZQ_SA_RSQRT
     const double ir = sa_rsqrt(q[0]);
     const double r0 = q[0] * ir;
-#else
-    const double r0 = sqrt(q[0]);
-    const double ir = sa_rcp(r0);
-#endif
     if constexpr (kRot) {
       double c, s;
       half_angle(e[0] * ir, g[0] * ir, e[0] >= 0.0, c, s);
@@ -154,11 +141,7 @@ __host__ __device__ __forceinline__ void sa_chain(double (&e)[M], double (&g)[M]
     }
     if constexpr (n > 1) {
       // theta' = (e g' - g e') / (2 q): w = num / q, g_next = -+ w / 2
-#if LZQ_SA_RSQRT
       const double iq = ir * ir;
-#else
-      const double iq = sa_rcp(q[0]);
-#endif
       double w[n - 1];
 #pragma unroll
       for (int l = 0; l < n - 1; ++l) {
@@ -204,13 +187,8 @@ template <int N, bool kRot, bool kEG>
 __host__ __device__ __forceinline__ void sa_levels_linear(double Dh, double sg, double mh, SU2& u, double* ev, double* gv) {
   // q = (Dh + sg h)^2 + mh^2 = [E^2, 2 sg Dh, 1]
   const double q0 = __builtin_fma(Dh, Dh, mh * mh), q1 = 2.0 * sg * Dh;
-#if LZQ_SA_RSQRT
   const double iE = sa_rsqrt(q0);
   const double E = q0 * iE;
-#else
-  const double E = sqrt(q0);
-  const double iE = sa_rcp(E);
-#endif
   if constexpr (kRot) {
     double c, s;
     half_angle(Dh * iE, mh * iE, Dh >= 0.0, c, s);
@@ -237,11 +215,7 @@ __host__ __device__ __forceinline__ void sa_levels_linear(double Dh, double sg, 
       if (l % 2 == 0) acc = __builtin_fma(e[l / 2], e[l / 2], acc);
       e[l] = ((l == 2 ? 1.0 : 0.0) - acc) * h0;
     }
-#if LZQ_SA_RSQRT
     const double iq = iE * iE;
-#else
-    const double iq = sa_rcp(q0);
-#endif
     double w[M];
     w[0] = -mh * sg * iq;
 #pragma unroll
@@ -338,9 +312,6 @@ __host__ __device__ __forceinline__ double sa_phase(double ta, double tb, double
   const double ulo = fmin(u1, u2), uhi = fmax(u1, u2);
   const double half = 0.5 * (uhi - ulo), mid = 0.5 * (uhi + ulo);
   double acc = 0.0;
-#ifndef LZQ_SA_PHASE_UNROLL
-#define LZQ_SA_PHASE_UNROLL 1  // the 4 Gauss points one after another (2, 4: side by side, tools/ablate_prop.py)
-#endif
 #pragma unroll LZQ_SA_PHASE_UNROLL
   for (int k = 0; k < 4; ++k) {
     const double u = __builtin_fma(half, gx[k], mid);
@@ -379,9 +350,6 @@ __host__ __device__ __forceinline__ SU2 sa_reflect(const SU2& u) {
 // state, so lz_follow_kernel computes them ahead of the propagation.  The core-edge frame is
 // computed once (the one at -tau_c by sa_reflect), and one frame per loop iteration: two side by
 // side (they are independent) would need ~250 VGPRs.
-#ifndef LZQ_FOLLOW_PAIR
-#define LZQ_FOLLOW_PAIR 0  // 1: the two outer frames (and phases) side by side after the core's (tools/ablate_prop.py)
-#endif
 __host__ __device__ __forceinline__ SU2 sa_frame(double tau, double sg, double mh, bool outer) {
   const double Ef2 = tau * tau + mh * mh, Ef4 = Ef2 * Ef2, Ef12 = Ef4 * Ef4 * Ef4;
   const bool far6 = outer && kSAFarC * fmax(mh, kSAMFloor) <= 0.1 * kSATol * Ef12 * sqrt(Ef2);
@@ -397,21 +365,7 @@ __host__ __device__ __forceinline__ void sa_store(const SU2& m, double* out) {
 }
 __host__ __device__ __forceinline__ void sa_cell_follow(double mh, double sg, double tl, double tr, double tau_c,
                                                         bool has_left, bool has_right, double* out) {
-#if LZQ_FOLLOW_PAIR
-  if (!(has_left || has_right)) return;
-  const SU2 uc = sa_frame(tau_c, sg, mh, false);
-  // both outer stretches in one straight block (the compiler interleaves the independent chains);
-  // a side that is absent evaluates the other's arguments and is not stored
-  const double ta = has_left ? tl : tr, tb = has_right ? tr : tl;
-  const SU2 ua = sa_frame(ta, sg, mh, true), ub = sa_frame(tb, sg, mh, true);
-  const double pa = sa_phase(ta, -tau_c, mh), pb = sa_phase(tau_c, tb, mh);
-  if (has_left) sa_store(su2_mul(sa_reflect(uc), su2_phase_adj(pa, ua)), out);
-  if (has_right) sa_store(su2_mul(ub, su2_phase_adj(pb, uc)), out + 4);
-#else
   SU2 uc;
-#ifndef LZQ_FOLLOW_JOB_UNROLL
-#define LZQ_FOLLOW_JOB_UNROLL 1  // 3: the three frames straight-line (tools/ablate_follow.sh)
-#endif
 #pragma unroll LZQ_FOLLOW_JOB_UNROLL
   for (int job = 0; job < 3; ++job) {
     if ((job == 0 && !(has_left || has_right)) || (job == 1 && !has_left) || (job == 2 && !has_right)) continue;
@@ -430,11 +384,8 @@ __host__ __device__ __forceinline__ void sa_cell_follow(double mh, double sg, do
     else
       sa_store(su2_mul(u, su2_phase_adj(sa_phase(tau_c, tr, mh), uc)), out + 4);           // U(tr) P U(tau_c)^+
   }
-#endif
 }
 
-#if LZQ_SA_CONTRACT
 #pragma clang fp contract(off)
-#endif
 
 }  // namespace lzq

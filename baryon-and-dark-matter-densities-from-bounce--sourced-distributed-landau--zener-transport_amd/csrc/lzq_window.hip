@@ -52,9 +52,6 @@ __global__ __launch_bounds__(kBlock, LZQ_MIN_WAVES) void yields_points_window_ke
 
 // lzq_yields_batch_reuse_window: points_reuse_kernel (lzq_kernels.hip) with the window of win[idx];
 // the tables are points_ztable_kernel's (header: y grid, c and z grid, LZQ_REUSE_TABLE_HEADER doubles)
-#ifndef LZQ_REUSE_MIN_WAVES
-#define LZQ_REUSE_MIN_WAVES 8
-#endif
 __global__ __launch_bounds__(kBlock, LZQ_REUSE_MIN_WAVES) void points_reuse_window_kernel(
     const lzq_point* __restrict__ pts, const lzq_window* __restrict__ win, lzq_window_tables wt, int64_t n,
     int32_t n_y, const double* __restrict__ Pov, double key_nz, double key_z_max, const int32_t* __restrict__ tidx,

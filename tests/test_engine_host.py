@@ -2,6 +2,7 @@
 puts points with equal stage keys next to each other so that whole wavefronts qualify for the
 integrator's cooperative mode."""
 import os
+import sys
 import numpy as np
 import torch
 
@@ -150,7 +151,9 @@ def test_build_variants_refuses_a_name_no_source_reads():
     """tools/build_variants.py takes a define only if csrc/ has an `#ifndef` (or, for a debug switch
     without a default, an `#ifdef`) for it: its own GRID and CONFIGS pass, the tuning parameters, the
     five pinned z-sum switches and the switches its users' docstrings name pass, and a name that no
-    source reads is refused by name instead of building the default library again."""
+    source reads is refused by name instead of building the default library again.  The settled A/B
+    switches of the ODE, propagator and profile units were folded into the code: their names are
+    refused, the numeric parameters and debug switches those units keep pass."""
     import sys
     import pytest
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tools"))
@@ -162,14 +165,57 @@ def test_build_variants_refuses_a_name_no_source_reads():
     bv.check_names([{"LZQ_KUNROLL": 4, "LZQ_MIN_WAVES": 4}, {"LZQ_TABBITS": 12}, {"LZQ_BLOCK": 256, "LZQ_YB": 2},
                     {"LZQ_SQFORM": 0, "LZQ_POLYDEG": 3}, {"LZQ_PROF_PAIR": 0}, {"LZQ_ODE_COOP_DEBUG": 1},
                     {n: 0 for n in ("LZQ_ZERO_SEG", "LZQ_DEAD_SEG", "LZQ_FROZEN_SEG", "LZQ_GROUP_SEG", "LZQ_PASS_LEAN")}])
+    kept = ("LZQ_ODE_MIN_WAVES", "LZQ_RIC_MIN_WAVES", "LZQ_RIC_TAB_MIN_WAVES", "LZQ_QUAD_MIN_WAVES",
+            "LZQ_PROP_MIN_WAVES", "LZQ_FOLLOW_MIN_WAVES", "LZQ_PROF_MIN_WAVES", "LZQ_REUSE_MIN_WAVES",
+            "LZQ_QUAD_UNROLL", "LZQ_PROP_UNROLL", "LZQ_SA_PHASE_UNROLL", "LZQ_FOLLOW_JOB_UNROLL",
+            "LZQ_ODE_MIN_GROUP", "LZQ_ODE_ROWS_COPY", "LZQ_ODE_ROWS_BLOCK", "LZQ_ODE_PRED_BLOCK", "LZQ_PROF_KEY_BINS",
+            "LZQ_ODE_COOP_DEBUG", "LZQ_ODE_TP_DEBUG", "LZQ_PROF_PAIR", "LZQ_TABBITS", "LZQ_POLYDEG", "LZQ_SQFORM")
+    bv.check_names([{n: 1} for n in kept])
     with pytest.raises(SystemExit, match="LZQ_NO_SUCH_SWITCH"):
         bv.check_names([{"LZQ_KUNROLL": 4}, {"LZQ_NO_SUCH_SWITCH": 1}])
+    for retired in ("LZQ_ODE_TNEWTON", "LZQ_FOLLOW_SPLIT", "LZQ_PROF_STAGE"):
+        with pytest.raises(SystemExit, match=retired):
+            bv.check_names([{"LZQ_KUNROLL": 4}, {retired: 0}])
     with pytest.raises(SystemExit, match="LZQ_NO_SUCH_SWITCH"):   # the command line is checked before anything is built
         argv, sys.argv = sys.argv, ["build_variants.py", "LZQ_YB=2,LZQ_NO_SUCH_SWITCH=1"]
         try:
             bv.main()
         finally:
             sys.argv = argv
+
+
+def test_compare_libraries_tells_same_machine_code_from_different(tmp_path):
+    """codeobj.compare_libraries (tools/compare_codeobj.py): a build compared with itself is the same
+    machine code; lzq_propagator.hip built with LZQ_PROP_UNROLL=1 is not, and the report names
+    lz_propagate_kernel (the kernel whose step loop the parameter unrolls).  One translation unit,
+    compiled twice for gfx950 on the CPU."""
+    import subprocess
+    b, co = pkg("build"), pkg("codeobj")
+    flags = [f for f in b.FLAGS if f != "-shared"]
+    objs = {}
+    for name, defs in (("default", []), ("unroll1", ["-DLZQ_PROP_UNROLL=1"])):
+        objs[name] = str(tmp_path / (name + ".o"))
+        subprocess.run([b.hipcc(), *flags, *defs, "-I", b.INCLUDE, "-c", os.path.join(b.CSRC, "lzq_propagator.hip"),
+                        "-o", objs[name]], check=True)
+    same = co.compare_libraries(objs["default"], objs["default"])
+    assert same["same"] and len(same["objects"]) == 1
+    o = same["objects"][0]
+    assert o["text_equal"] and o["note_equal"] and o["tables_equal"] and not o["descriptors_differ"]
+    assert not o["isa_differ"] and not o["only_in_a"] and not o["only_in_b"]
+    assert any("lz_propagate_kernel" in k for k in o["kernels"]) and any("lz_follow_kernel" in k for k in o["kernels"])
+    diff = co.compare_libraries(objs["default"], objs["unroll1"])
+    assert not diff["same"]
+    o = diff["objects"][0]
+    assert not o["text_equal"] and not o["same"]
+    assert any("lz_propagate_kernel" in k for k in o["isa_differ"])
+    assert not any("lz_follow_kernel" in k for k in o["isa_differ"])     # the parameter does not reach it
+    # the command-line wrapper: its exit status, the named kernel and the verdict line
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(b.HERE), "tools", "compare_codeobj.py"),
+                        objs["default"], objs["unroll1"]], capture_output=True, text=True)
+    assert r.returncode == 1 and "lz_propagate_kernel" in r.stdout and "DIFFERENT machine code" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(b.HERE), "tools", "compare_codeobj.py"),
+                        objs["default"], objs["default"]], capture_output=True, text=True)
+    assert r.returncode == 0 and "same machine code" in r.stdout
 
 
 def test_build_stamp_tracks_content():

@@ -300,7 +300,7 @@ def test_ode_quadrature_sweep_shared_and_deterministic(gpu_engine):
 
 
 def test_ode_linear_waves_bit_identical(gpu_engine):
-    """The linear-wave fast path (lzq_ode.hip LZQ_ODE_LINFAST: sigma_v = 0 on every lane of a
+    """The linear-wave fast path (lzq_ode.hip, ode_integrate_kernel<kLin>: sigma_v = 0 on every lane of a
     cooperative wave with one Gamma_wash per segment; a regular step is Y_B's shared affine map,
     plus Y_chi's three depletion fmas) gives the per-lane mode's bits: wash-out with and without
     depletion, thermal and non-thermal starts, a window crossing T = m/3 (split steps take the
@@ -660,7 +660,7 @@ def test_ode_cooperative_subgroups_bit_identical(gpu_engine):
 
 def test_ode_riccati_segments_bit_identical(gpu_engine):
     """Waves of uniform 16- and 8-lane segments (fewer points per stage key than a wave), each
-    segment on one table with one Gamma_wash: ode_riccati_kernel<., false, true> (LZQ_ODE_RICSEG)
+    segment on one table with one Gamma_wash: ode_riccati_kernel<., false, true>
     steps them, every segment with its own window, N and step size -- without a T = m/3 split in
     the window (pass 0 alone) and with one (m_chi ~ 40 on the narrow window: the three passes, each
     segment's split at its own step).  The per-lane mode's bits, in one launch and as continuation

@@ -66,7 +66,7 @@ def test_stokes_phase_series_vs_mpmath():
 
 
 def test_magnus_vector_polynomials_in_D():
-    """Round 4 (lzq_propagator.hip, LZQ_PROP_POLY): the kernel evaluates the eighth-order Magnus
+    """Round 4 (lzq_propagator.hip): the kernel evaluates the eighth-order Magnus
     vector as per-cell polynomials in the step's midpoint D = D0 + i dD; the expansion in
     E^2 = D^2 + m^2 is an identity of the header's per-step expressions (checked in exact
     rational arithmetic), and D0 + i dD is the midpoint slope (cl + (i + 1/2) h - xc)."""
