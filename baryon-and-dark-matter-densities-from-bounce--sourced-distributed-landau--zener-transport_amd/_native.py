@@ -157,6 +157,10 @@ FIELD.update({"delta_LZ": 32, "m_mix": 33, "dprime": 34})
 # *_window grid entry points only
 WINDOW_FIELD = {"window_y0": 64, "window_half_width": 65, "window_sigma_lo": 66, "window_sigma_hi": 67,
                 "window_sigma": 68, "window_scale": 69, "window_table": 70}
+# LZQ_F_GAMMA_WASH / LZQ_F_DEPLETE: the axes over a point's lzq_ode_params block, accepted by the *_wash
+# entry points only (wash.py)
+WASH_FIELD = {"Gamma_wash_over_H": 96, "deplete_DM_from_source": 97}
+WASH_NZ_CONT = -1  # LZQ_WASH_NZ_CONT
 FERMION, BOSON = 0, 1
 THERMAL, NONTHERMAL, REGIME_OTHER = 0, 1, 2
 LZQ_NZ, LZQ_Z_MAX = 1200, 30.0  # fpy:142 AoverVKernel defaults, main()'s grid (fpy:197)
@@ -213,6 +217,8 @@ EXPORTS = ("lzq_abi_version", "lzq_last_error", "lzq_init", "lzq_zgrid_init", "l
            "lzq_sweep_grid_solve_cont",
            "lzq_fk_check_host", "lzq_fk_pbar_host", "lzq_fk_pbar_batch", "lzq_fk_nodes", "lzq_fk_table_stride",
            "lzq_fk_tables", "lzq_yields_batch_reuse_fk",
+           "lzq_wash_check_host", "lzq_wash_factor_host", "lzq_wash_factor_batch", "lzq_yields_batch_reuse_wash",
+           "lzq_sweep_grid_from_ztables_wash", "lzq_sweep_grid_solve_wash", "lzq_solve_check_host_wash",
            "lzq_lz_propagate", "lzq_lz_propagate_v", "lzq_ode_tables", "lzq_ode_integrate", "lzq_ode_integrate_shared", "lzq_ode_rows", "lzq_ode_integrate_rows", "lzq_ode_integrate_tp", "lzq_ode_quadrature", "lzq_ode_batch",
            "lzq_ode_aov_T", "lzq_ode_rhs", "lzq_profile_splines", "lzq_profile_crossings",
            "lzq_lz_propagate_profile",
@@ -313,6 +319,16 @@ def load(path: str | None = None):
     L.lzq_fk_tables.argtypes = [vp, vp, vp, vp, i64, i32, vp, i64, vp, vp]
     L.lzq_yields_batch_reuse_fk.argtypes = [vp, i64, i32, i32, d, vp, vp, vp, vp, i64, vp, vp, i64, vp,
                                             P(LzqWindowTables), vp, vp]
+    L.lzq_wash_check_host.argtypes = [vp, i64]
+    L.lzq_wash_factor_host.argtypes = [P(LzqPoint), P(LzqOdeParams), vp, i64, vp]
+    L.lzq_wash_factor_batch.argtypes = [P(LzqPoint), P(LzqOdeParams), vp, i64, vp, vp]
+    L.lzq_yields_batch_reuse_wash.argtypes = [vp, i64, i32, i32, d, vp, vp, vp, i64, vp, i64, vp,
+                                              P(LzqWindowTables), vp, vp, vp]
+    L.lzq_sweep_grid_from_ztables_wash.argtypes = [P(LzqPoint), P(LzqWindow), P(LzqOdeParams), P(LzqAxis), i32, i64,
+                                                   i64, i32, i32, d, vp, vp, i64, P(LzqWindowTables), vp, vp]
+    L.lzq_sweep_grid_solve_wash.argtypes = [P(LzqPoint), P(LzqWindow), P(LzqOdeParams), P(LzqAxis), i32, P(LzqSolve),
+                                            i64, i64, i32, i32, d, vp, vp, i64, P(LzqWindowTables), vp, vp, vp]
+    L.lzq_solve_check_host_wash.argtypes = [P(LzqSolve), P(LzqWindow), P(LzqOdeParams), P(LzqAxis), i32]
     L.lzq_lz_propagate.argtypes = [vp, vp, vp, i64, i32, d, d, i32, vp, vp]
     L.lzq_lz_propagate_v.argtypes = [vp, vp, vp, vp, i64, i32, d, i32, vp, vp]
     L.lzq_ode_tables.argtypes = [vp, i64, vp, vp, i32, i32, d, vp, vp, i64, vp, vp]

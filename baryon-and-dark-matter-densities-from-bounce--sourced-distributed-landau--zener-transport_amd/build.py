@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.normpath(os.path.join(HERE, "..", "include"))
 BUILD_DIR = os.path.join(HERE, "_build")
 LIB_PATH = os.path.join(BUILD_DIR, "liblzq.so")
-SOURCES = ["lzq_kernels.hip", "lzq_aov.hip", "lzq_window.hip", "lzq_solve.hip", "lzq_cont.hip", "lzq_fk.hip", "lzq_propagator.hip", "lzq_ode.hip", "lzq_ode_tp.hip", "lzq_profile.hip",
+SOURCES = ["lzq_kernels.hip", "lzq_aov.hip", "lzq_window.hip", "lzq_solve.hip", "lzq_cont.hip", "lzq_fk.hip", "lzq_wash.hip", "lzq_propagator.hip", "lzq_ode.hip", "lzq_ode_tp.hip", "lzq_profile.hip",
            "lzq_fit.hip", "lzq_post.hip", "lzq_obs.hip", "lzq_rank.hip"]
 # every header next to the sources (tests/test_engine_host.py checks each #include "..." of the
 # sources resolves to one of the build inputs)

@@ -13,7 +13,7 @@ import torch
 
 import logging
 
-from . import _native, fit as _fit, fk as _fk, solve as _solve, window as _window
+from . import _native, fit as _fit, fk as _fk, solve as _solve, wash as _wash, window as _window
 from .config import to_aov, to_ctypes_aov, to_ctypes_ode, to_ctypes_point, to_point
 
 _log = logging.getLogger("lzq")
@@ -175,6 +175,18 @@ class Engine:
         self._keepalive_win = (None, d_wt)
         return out
 
+    def wash_factor(self, point, wash, ys) -> torch.Tensor:
+        """The wash-out factor omega(T(y)) of one point (a 1-record POINT_DTYPE array) and block at every
+        y on the device (lzq_wash_factor_batch): the wash kernels' factor evaluated alone."""
+        pt = _native.LzqPoint.from_buffer_copy(np.ascontiguousarray(point).reshape(1).tobytes())
+        ob = _wash.to_ctypes(wash)
+        y = self._f64(ys).reshape(-1)
+        out = torch.empty_like(y)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.lzq_wash_factor_batch(ctypes.byref(pt), ctypes.byref(ob), _vp(y), y.numel(), _vp(out),
+                                                       self._stream()))
+        return out
+
     # -- fpy:158-165 -----------------------------------------------------------------------
     def aov(self, kernel, ys, nz: int = _native.LZQ_NZ, z_max: float = _native.LZQ_Z_MAX,
             continuum: bool = False) -> torch.Tensor:
@@ -210,7 +222,7 @@ class Engine:
     # -- fpy:231-267 + epilogue ----------------------------------------------------------------
     def yields(self, points, n_y: int = 8000, T_lo=None, T_hi=None, P=None, reuse: bool = False,
                nz: int = _native.LZQ_NZ, z_max: float = _native.LZQ_Z_MAX, aov=None, window=None,
-               window_tables=None, continuum: bool = False, fk=None, fk_delta=None) -> torch.Tensor:
+               window_tables=None, continuum: bool = False, fk=None, fk_delta=None, wash=None) -> torch.Tensor:
         """points: POINT_DTYPE numpy array or a device byte tensor from points_to_device.
         Returns (n, 6) float64 device tensor in YIELD_FIELDS order.
         reuse: lzq_yields_batch_reuse -- points equal in _native.ZSUM_KEY share one table of
@@ -233,7 +245,17 @@ class Engine:
         constant P (csrc/lzq_fk.h); fk_delta is delta_0 per point (PAPER eq. (8) at F = 1; one value or n),
         by default -log1p(-P)/(2 pi) from each point's P_chi_to_B.  Always from shared z-sum tables, the
         linspace grid's or with `continuum` the continuum rule's; `points` is then a host array.  With a
-        window or main()'s; not with `aov`, `P`, T_lo or T_hi."""
+        window or main()'s; not with `aov`, `P`, T_lo or T_hi.
+        wash: wash-out and source depletion on the y-grid (include/lzq.h "wash-out and source depletion";
+        wash.to_wash): one block {sigma_v_chi_GeV_m2, Gamma_wash_over_H, deplete_DM_from_source} for all
+        points or n ODE_DTYPE records, sigma_v = 0 everywhere.  Always from shared z-sum tables, the
+        linspace grid's or with `continuum` the continuum rule's; with a window or main()'s; not with `aov`,
+        `fk`, T_lo or T_hi."""
+        if wash is not None:
+            if aov is not None or fk is not None or T_lo is not None or T_hi is not None:
+                raise ValueError("yields: wash runs from shared z-sum tables (main()'s T range) and combines with "
+                                 "a window and the continuum rule only (not aov, fk, T_lo, T_hi)")
+            return self._yields_wash(points, int(n_y), nz, z_max, continuum, P, window, window_tables, wash)
         if fk is None and fk_delta is not None:
             raise ValueError("yields: fk_delta without fk")
         if fk is not None:
@@ -402,6 +424,55 @@ class Engine:
                 lo = hi
         return out
 
+    def _yields_wash(self, points, n_y, nz, z_max, continuum, P, window, window_tables, wash) -> torch.Tensor:
+        """Engine.yields(wash=...): lzq_yields_batch_reuse_wash on one table per distinct
+        _native.ZSUM_KEY (`reuse`'s grouping); tables beyond REUSE_MAX_BYTES raise (there is no dense
+        form)."""
+        if continuum:
+            z_max, nz = _native.cont_z_max(z_max), _native.WASH_NZ_CONT
+        else:
+            nz, z_max = _native.zgrid(nz, z_max)
+        d_pts = points if isinstance(points, torch.Tensor) else self.points_to_device(points)
+        n = d_pts.numel() // _native.POINT_DTYPE.itemsize
+        if isinstance(wash, torch.Tensor):
+            if wash.numel() != n * _native.ODE_DTYPE.itemsize:
+                raise ValueError("wash: need one lzq_ode_params record per point")
+            d_ode = wash
+        else:
+            d_ode = self.ode_params_to_device(_wash.check(_wash.to_washes(wash, n), self.lib))
+        d_win = d_wt = None
+        if window is not None:
+            d_wt = self.window_tables_to_device(window_tables)
+            d_win = self.window_to_device(window, n, d_wt)
+        elif window_tables is not None:
+            raise ValueError("yields: window_tables without a window")
+        out = torch.empty((n, 6), dtype=torch.float64, device=self.device)
+        Pv = None if P is None else self._f64(P)
+        if n == 0:
+            return out
+        with torch.cuda.device(self.device):
+            groups = table_groups(d_pts, n, _ZSUM_WORDS)
+            if groups is None:   # one point, or sharing would not pay: a table per point
+                ar = torch.arange(n, dtype=torch.int64, device=self.device)
+                groups = (ar, ar)
+            rep, inv = groups
+            stride = max(n_y, 2000) + _native.REUSE_TABLE_HEADER
+            need = rep.numel() * stride
+            if need * 8 > REUSE_MAX_BYTES:
+                raise ValueError(f"wash: {rep.numel()} z-sum tables exceed REUSE_MAX_BYTES; the wash-out "
+                                 "quadrature runs from the shared tables only")
+            if self._zwork is None or self._zwork.numel() < need:
+                self._zwork = torch.empty(need, dtype=torch.float64, device=self.device)
+            self._ztab_key = None   # the grid tables in _zwork are overwritten
+            idx = inv.to(torch.int32)
+            self._check(self.lib.lzq_yields_batch_reuse_wash(
+                _vp(d_pts), n, n_y, nz, z_max, _vp(Pv), _vp(rep), _vp(idx), rep.numel(), _vp(self._zwork),
+                self._zwork.numel(), _vp(d_win), d_wt.arg if d_wt is not None else None, _vp(d_ode), _vp(out),
+                self._stream()))
+            self._keepalive_reuse = (rep, idx, d_pts, d_win, d_wt, d_ode)
+            self.last_yields_path = "tables"
+        return out
+
     def _yields_cont(self, d_pts, n, n_y, z_max, Pv, d_win, d_wt, out) -> None:
         """Engine.yields(continuum=True): lzq_yields_batch_cont per chunk of points whose tables fit
         REUSE_MAX_BYTES (one chunk unless nearly every point has a z-sum key of its own)."""
@@ -446,7 +517,7 @@ class Engine:
               out: Optional[torch.Tensor] = None, P: Optional[float] = None,
               P_points: Optional[torch.Tensor] = None, reuse: bool = False, nz: int = _native.LZQ_NZ,
               z_max: float = _native.LZQ_Z_MAX, window=None, window_tables=None, solve=None,
-              continuum: bool = False):
+              continuum: bool = False, wash=None):
         """axes: sequence of (field_name, values) (C order, last fastest); field names are
         the lzq_point double fields or 'delta_LZ' / 'm_mix' / 'dprime'.  P_points: optional
         per-point P override ([count], device), e.g. from lz_propagate (config C5).
@@ -470,7 +541,16 @@ class Engine:
         (there is no dense solve).  Every host-side refusal raises ValueError before any upload.
         continuum: the z-sums on the continuum z rule of z_max (include/lzq.h "A/V in the continuum
         limit"; nz is not read).  Always through the shared z-sum tables, like a solve: tables beyond
-        REUSE_MAX_BYTES raise (there is no dense continuum path)."""
+        REUSE_MAX_BYTES raise (there is no dense continuum path).
+        wash: wash-out and source depletion on the y-grid (include/lzq.h "wash-out and source depletion"):
+        the base block {sigma_v_chi_GeV_m2 = 0, Gamma_wash_over_H, deplete_DM_from_source} (wash.to_wash);
+        axes may then carry 'Gamma_wash_over_H' and 'deplete_DM_from_source' (value != 0), decoded in the
+        kernel like the point's own fields, and a solve may take 'Gamma_wash_over_H' as its field.  Always
+        through the shared z-sum tables (the wash axes contribute none); combines with window, solve and
+        continuum."""
+        if wash is not None:
+            return self._sweep_wash(base_cfg, axes, start, count, int(n_y), out, P, P_points, nz, z_max, window,
+                                    window_tables, solve, continuum, wash)
         if continuum:
             z_max = _native.cont_z_max(z_max)
             reuse = True
@@ -599,12 +679,109 @@ class Engine:
         self._keepalive = (dev_vals, d_wt)  # axis buffers (and window tables) must outlive the async launch
         return out
 
+    def _sweep_wash(self, base_cfg, axes, start, count, n_y, out, P, P_points, nz, z_max, window, window_tables,
+                    solve, continuum, wash):
+        """Engine.sweep(wash=...): the tables of lzq_sweep_grid_ztables[_window|_cont] for the axis list
+        without the wash axes (built once per grid, as with `reuse`), then
+        lzq_sweep_grid_from_ztables_wash or, with a solve, lzq_sweep_grid_solve_wash."""
+        if continuum:
+            z_max, key_nz = _native.cont_z_max(z_max), _native.WASH_NZ_CONT
+        else:
+            nz, z_max = _native.zgrid(nz, z_max)
+            key_nz = nz
+        if len(axes) > _native.LZQ_MAX_AXES:
+            raise ValueError(f"at most {_native.LZQ_MAX_AXES} sweep axes")
+        ob = _wash.to_ctypes(_wash.check(_wash.to_wash(wash), self.lib))
+        names = [n for n, _ in axes]
+        sv = None
+        if solve is not None:
+            if P_points is not None and _solve.normalize(solve)["field"] in ("P_chi_to_B", "delta_LZ", "m_mix", "dprime"):
+                raise ValueError("solve: a per-point P override (P_points) together with a solve for P or an LZ field")
+            sv = _solve.to_ctypes(_solve.check(solve, names, window, self.lib, wash=_wash.to_wash(wash)))
+        win = d_wt = None
+        if window is not None:
+            d_wt = self.window_tables_to_device(window_tables)
+            rec = _window.to_window(window)
+            _window.grid_check(rec, [(n, v) for n, v in axes
+                                     if n in _native.WINDOW_FIELD and not isinstance(v, torch.Tensor)], d_wt.host)
+            win = _native.LzqWindow.from_buffer_copy(rec.tobytes())
+        elif window_tables is not None:
+            raise ValueError("sweep: window_tables without a window")
+        for name in names:
+            if _wash.field_code(name) is None:
+                raise ValueError(f"unknown sweep field {name!r}")
+            if name in _native.WINDOW_FIELD and win is None:
+                raise ValueError(f"sweep field {name!r} needs a window")
+        for name, v in axes:   # host values of a Gamma axis: the library's refusals, before any upload
+            if name == "Gamma_wash_over_H" and not isinstance(v, torch.Tensor):
+                g = np.asarray(v, dtype=np.float64).reshape(-1)
+                blocks = np.repeat(_wash.to_wash(wash), g.size)
+                blocks["Gamma_wash_over_H"] = g
+                _wash.check(blocks, self.lib)
+        dev_vals = [self._f64(v).reshape(-1) for _, v in axes]
+        arr = (_native.LzqAxis * max(1, len(axes)))()
+        for a, (name, t) in enumerate(zip(names, dev_vals)):
+            arr[a].field, arr[a].n, arr[a].values = _wash.field_code(name), t.numel(), t.data_ptr()
+        # the table half sees the list without the wash axes (and, for a solve of m_mix / dprime, without
+        # the LZ axes): none of them contributes a table, so the workspace and the table indices are the same
+        drop = set(_native.WASH_FIELD)
+        if sv is not None and sv.field in (_native.FIELD["m_mix"], _native.FIELD["dprime"]):
+            drop |= {"m_mix", "dprime", "delta_LZ"}
+        keep = [a for a, n in enumerate(names) if n not in drop]
+        t_arr, t_n = (_native.LzqAxis * max(1, len(keep)))(), len(keep)
+        for k, a in enumerate(keep):
+            t_arr[k].field, t_arr[k].n, t_arr[k].values = arr[a].field, arr[a].n, arr[a].values
+        base = to_ctypes_point(to_point(base_cfg, P=P))
+        if out is None:
+            out = torch.empty((count, 6), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            Pp = None if P_points is None else self._f64(P_points).reshape(-1)
+            if Pp is not None and Pp.numel() != count:
+                raise ValueError("P_points must have `count` entries")
+            need = self.lib.lzq_sweep_grid_reuse_workspace(t_arr, t_n, n_y)
+            if need < 0:
+                self._check(int(need))
+            if need * 8 > REUSE_MAX_BYTES:
+                raise ValueError(f"wash: the grid's z-sum tables ({need * 8} bytes) exceed REUSE_MAX_BYTES; the "
+                                 "wash-out quadrature runs from the shared tables only")
+            tkey = ("wash-tables", bytes(base), win is not None,
+                    tuple((names[a], dev_vals[a].cpu().numpy().tobytes()) for a in keep), n_y, self._exp_variant,
+                    "continuum" if continuum else nz, z_max)
+            if tkey != self._ztab_key:
+                if self._zwork is None or self._zwork.numel() < need:
+                    self._zwork = torch.empty(max(int(need), 1), dtype=torch.float64, device=self.device)
+                if continuum:
+                    self._check(self.lib.lzq_sweep_grid_ztables_cont(
+                        ctypes.byref(base), t_arr, t_n, n_y, z_max, _vp(self._zwork), self._zwork.numel(),
+                        self._stream()))
+                else:
+                    ztables = self.lib.lzq_sweep_grid_ztables if win is None else self.lib.lzq_sweep_grid_ztables_window
+                    self._check(ztables(ctypes.byref(base), t_arr, t_n, n_y, nz, z_max, _vp(self._zwork),
+                                        self._zwork.numel(), self._stream()))
+                self._ztab_key = tkey
+            self.last_reuse = self.last_yields_path = "tables"
+            b_win = ctypes.byref(win) if win is not None else None
+            a_wt = d_wt.arg if d_wt is not None else None
+            self._keepalive = (dev_vals, d_wt)  # axis buffers (and window tables) must outlive the async launch
+            if sv is not None:
+                sol = torch.empty((count, 6), dtype=torch.float64, device=self.device)
+                self._check(self.lib.lzq_sweep_grid_solve_wash(
+                    ctypes.byref(base), b_win, ctypes.byref(ob), arr, len(axes), ctypes.byref(sv), int(start),
+                    int(count), n_y, key_nz, z_max, _vp(Pp), _vp(self._zwork), self._zwork.numel(), a_wt, _vp(out),
+                    _vp(sol), self._stream()))
+                return out, sol
+            self._check(self.lib.lzq_sweep_grid_from_ztables_wash(
+                ctypes.byref(base), b_win, ctypes.byref(ob), arr, len(axes), int(start), int(count), n_y, key_nz,
+                z_max, _vp(Pp), _vp(self._zwork), self._zwork.numel(), a_wt, _vp(out), self._stream()))
+        return out
+
     def solve_point(self, cfg, solve, window=None, window_tables=None, n_y: int = 8000, P: Optional[float] = None,
-                    nz: int = _native.LZQ_NZ, z_max: float = _native.LZQ_Z_MAX, continuum: bool = False):
+                    nz: int = _native.LZQ_NZ, z_max: float = _native.LZQ_Z_MAX, continuum: bool = False, wash=None):
         """The solve of one configuration: sweep(..., solve=solve) on a grid with no axes.  Returns
-        (record, result), two float64[6] device tensors."""
+        (record, result), two float64[6] device tensors.  wash: as for sweep (e.g. the Gamma_wash_over_H
+        at which DM_over_B = 5.357 with depletion on, PAPER §10 step 5)."""
         rec, sol = self.sweep(cfg, [], 0, 1, n_y=n_y, P=P, nz=nz, z_max=z_max, window=window,
-                              window_tables=window_tables, solve=solve, continuum=continuum)
+                              window_tables=window_tables, solve=solve, continuum=continuum, wash=wash)
         return rec[0], sol[0]
 
     # -- sweep fits, posteriors, observables, ranked points (lzq_fit_*, lzq_post_*, lzq_obs_*,

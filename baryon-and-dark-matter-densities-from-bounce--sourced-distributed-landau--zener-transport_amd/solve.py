@@ -36,7 +36,7 @@ def normalize(solve: Mapping) -> dict:
         if k not in solve:
             raise ValueError(f"solve: missing {k!r}")
     name = str(solve["field"])
-    if name not in _native.FIELD and name not in _native.WINDOW_FIELD:
+    if name not in _native.FIELD and name not in _native.WINDOW_FIELD and name not in _native.WASH_FIELD:
         raise ValueError(f"solve: unknown field {name!r}")
     target = dict(DEFAULT_TARGET, **dict(solve.get("target") or {}))
     if set(target) != {"field", "value"}:
@@ -54,18 +54,26 @@ def normalize(solve: Mapping) -> dict:
 
 def to_ctypes(solve: Mapping) -> "_native.LzqSolve":
     s = normalize(solve)
-    field = _native.FIELD.get(s["field"], _native.WINDOW_FIELD.get(s["field"]))
+    field = _native.FIELD.get(s["field"], _native.WINDOW_FIELD.get(s["field"], _native.WASH_FIELD.get(s["field"])))
     return _native.LzqSolve(field, _native.YIELD_FIELDS.index(s["target"]["field"]), s["lo"], s["hi"],
                             s["target"]["value"], s["xtol"], s["max_evals"])
 
 
-def check(solve: Mapping, axis_names: Sequence[str], window_block=None, lib=None) -> dict:
+def check(solve: Mapping, axis_names: Sequence[str], window_block=None, lib=None, wash=None) -> dict:
     """Every host-side refusal of the solve (include/lzq.h), before anything is uploaded: raises
     ValueError with the library's message.  axis_names: the grid's axes; window_block: the base window
-    (anything but None counts as "the sweep has a window").  Returns the normalized spec."""
+    (anything but None counts as "the sweep has a window"); wash: the base wash block of a sweep through
+    the wash-out quadrature (wash.py), where Gamma_wash_over_H is a solve field too.  Returns the
+    normalized spec."""
     s = normalize(solve)
     if s["field"] in _native.WINDOW_FIELD and window_block is None:
         raise ValueError(f"solve: window field {s['field']!r} needs a window")
+    if wash is not None:
+        from . import wash as _wash
+        _wash.solve_check(to_ctypes(s), axis_names, wash, window_block, lib)
+        return s
+    if s["field"] in _native.WASH_FIELD:
+        raise ValueError(f"solve: field {s['field']!r} needs the wash-out quadrature (wash=...)")
     L = lib or _native.load()
     n = len(axis_names)
     if n > _native.LZQ_MAX_AXES:

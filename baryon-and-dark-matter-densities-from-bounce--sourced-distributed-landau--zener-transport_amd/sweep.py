@@ -219,6 +219,10 @@ class SweepSpec:
     # continuum z rule of z_max (include/lzq.h "A/V in the continuum limit"; nz is then not read)
     z_rule: str = "linspace"
     fk: Optional[FkSpec] = None   # None: the paper's F = 1 (one P per point)
+    # "ode": Gamma_wash / depletion points take the ODE fallback, as the reference's fpy:372 sends them;
+    # "quadrature" (opt-in): with sigma_v = 0 everywhere they run on the y-grid quadrature (include/lzq.h
+    # "wash-out and source depletion"), where window, solve, --reuse-zsums and the continuum rule apply
+    wash_rule: str = "ode"
 
     @property
     def continuum(self) -> bool:
@@ -260,6 +264,8 @@ class SweepSpec:
             d["z_rule"] = self.z_rule
         if self.fk is not None:
             d["fk"] = self.fk.to_json()
+        if self.wash_rule != "ode":
+            d["wash_rule"] = self.wash_rule
         return d
 
     def axis_values(self, start: int, count: int, device) -> dict:
@@ -303,11 +309,68 @@ ODE_FIELDS = ("sigma_v_chi_GeV_m2", "Gamma_wash_over_H", "deplete_DM_from_source
 
 
 def is_ode_spec(spec: "SweepSpec") -> bool:
-    """Does any point of the sweep leave the fast path (fpy:372) for the ODE fallback?"""
+    """Does any point of the sweep leave the fast path (fpy:372) for the ODE fallback?  (Not under
+    "wash_rule": "quadrature", whose wash-out / depletion points stay on the y-grid: check_wash_spec.)"""
+    if spec.wash_rule == "quadrature":
+        return False
     b = spec.base
     base_ode = bool(b.get("deplete_DM_from_source")) or float(b.get("sigma_v_chi_GeV_m2", 0.0)) != 0.0 or \
         float(b.get("Gamma_wash_over_H", 0.0)) != 0.0
     return base_ode or any(name in ODE_FIELDS and np.any(np.asarray(v) != 0) for name, v in spec.axes)
+
+
+def uses_wash(spec: "SweepSpec") -> bool:
+    """Does the sweep run through the wash-out quadrature's kernels (Engine.sweep(wash=))?  Under
+    "wash_rule": "quadrature", when its base or axes set Gamma_wash_over_H / deplete_DM_from_source or its
+    solve asks for Gamma_wash_over_H; a spec without any of it takes the routes it takes today."""
+    if spec.wash_rule != "quadrature":
+        return False
+    b = spec.base
+    if bool(b.get("deplete_DM_from_source")) or float(b.get("Gamma_wash_over_H", 0.0)) != 0.0:
+        return True
+    if any(name in _native.WASH_FIELD for name, _ in spec.axes):
+        return True
+    return spec.solve is not None and _solve.normalize(spec.solve)["field"] in _native.WASH_FIELD
+
+
+def wash_block(spec: "SweepSpec") -> dict:
+    """The base block of a wash sweep (wash.to_wash's mapping)."""
+    b = spec.base
+    return {"sigma_v_chi_GeV_m2": float(b.get("sigma_v_chi_GeV_m2", 0.0) or 0.0),
+            "Gamma_wash_over_H": float(b.get("Gamma_wash_over_H", 0.0) or 0.0),
+            "deplete_DM_from_source": bool(b.get("deplete_DM_from_source"))}
+
+
+def check_wash_spec(spec: "SweepSpec") -> None:
+    """A "wash_rule" the sweep cannot run, as a ValueError: an unknown rule; with "quadrature" any
+    sigma_v != 0 (the Y_chi equation is then not linear: the ODE fallback's), a sigma_v axis at all (the
+    kernels decode no such field), a momentum kernel next to wash-out, window axes that collide, and
+    every value of a Gamma axis that the library refuses."""
+    if spec.wash_rule not in ("ode", "quadrature"):
+        raise ValueError(f"wash_rule must be 'ode' or 'quadrature', got {spec.wash_rule!r}")
+    if spec.wash_rule != "quadrature":
+        return
+    if float(spec.base.get("sigma_v_chi_GeV_m2", 0.0) or 0.0) != 0.0:
+        raise ValueError("wash_rule 'quadrature' with sigma_v_chi_GeV_m2 != 0 in the base: the linear form needs "
+                         "sigma_v = 0 everywhere (drop the rule for the ODE fallback)")
+    for n, v in spec.axes:
+        if n == "sigma_v_chi_GeV_m2":
+            raise ValueError("wash_rule 'quadrature' with a sigma_v_chi_GeV_m2 axis: the linear form needs sigma_v = 0 "
+                             "everywhere" + ("" if np.any(np.asarray(v) != 0) else " (an all-zero axis sweeps nothing: drop it)"))
+    if not uses_wash(spec):
+        return
+    if spec.fk is not None:
+        raise ValueError("an 'fk' section on a spec with wash-out or depletion under wash_rule 'quadrature': the "
+                         "momentum kernel together with wash-out is not built")
+    if spec.window is not None and window_axes_collide(spec):
+        raise ValueError("wash_rule 'quadrature' on a spec whose window axes collide (the grid entry points refuse them)")
+    from . import wash as _wash
+    for n, v in spec.axes:
+        if n == "Gamma_wash_over_H":
+            rec = np.repeat(_wash.to_wash(wash_block(spec)), len(v))
+            rec[n] = np.asarray(v, dtype=np.float64)
+            _wash.check(rec)
+    _wash.check(_wash.to_wash(wash_block(spec)))
 
 
 def grid_records(spec: "SweepSpec", start: int, count: int, engine=None):
@@ -438,7 +501,8 @@ def spec_from_json(d: dict) -> SweepSpec:
     spec = SweepSpec(d.get("name", "custom"), base, axes, int(d.get("n_y", 8000)), d.get("notes", ""), cr, method, prof,
                      nz, z_max, None if ms is None or int(ms) == 0 else int(ms), win,
                      _solve.normalize(d["solve"]) if d.get("solve") else None, d.get("z_rule", "linspace"),
-                     FkSpec.from_json(d["fk"]) if d.get("fk") is not None else None)
+                     FkSpec.from_json(d["fk"]) if d.get("fk") is not None else None, d.get("wash_rule", "ode"))
+    check_wash_spec(spec)
     check_z_rule(spec)
     check_fk_spec(spec)
     check_window_spec(spec)
@@ -476,7 +540,8 @@ def check_solve_spec(spec: SweepSpec) -> None:
                          "P override)")
     if spec.window is not None and window_axes_collide(spec):
         raise ValueError("a 'solve' section on a spec whose window axes collide (the grid entry points refuse them)")
-    _solve.check(sv, [n for n, _ in grid_axes_for_kernel(spec)], None if spec.window is None else spec.window.block)
+    _solve.check(sv, [n for n, _ in grid_axes_for_kernel(spec)], None if spec.window is None else spec.window.block,
+                 wash=wash_block(spec) if uses_wash(spec) else None)
 
 
 def check_fk_spec(spec: SweepSpec) -> None:
@@ -987,6 +1052,7 @@ def make_compute(spec: SweepSpec, engine, reuse: bool = False, window_host_recor
     window_host_records: a window spec through explicit host-built records even where the grid
     entry points would take it (the same bits; tools/bench_window.py's baseline)."""
     pcache = {}   # the profile's device splines, built once per sweep
+    check_wash_spec(spec)
     check_z_rule(spec)
     check_window_spec(spec)
     check_solve_spec(spec)
@@ -1005,6 +1071,26 @@ def make_compute(spec: SweepSpec, engine, reuse: bool = False, window_host_recor
                                     window_tables=d_tables))
             engine.last_reuse = engine.last_yields_path
         return compute_fk
+    if uses_wash(spec):
+        # wash-out / depletion on the y-grid (Engine.sweep(wash=)): always from the shared z-sum tables; the
+        # Gamma and depletion axes ride in the axis list and are decoded in the kernel, like the window's;
+        # with a solve the records at the solutions go to `out` and the results ride back on the function
+        d_tables = engine.window_tables_to_device(spec.window.host_tables()) if spec.window is not None else None
+
+        def compute_wash(s, n, out):
+            P_points = coherent_P(spec, s, n, engine) if spec.crossings is not None else None
+            if spec.profile is not None:
+                P_points = profile_P(spec, s, n, engine, pcache)
+            res = engine.sweep(spec.base, grid_axes_for_kernel(spec), s, n, n_y=spec.n_y, out=out, P_points=P_points,
+                               nz=spec.nz, z_max=spec.z_max, window=None if spec.window is None else spec.window.block,
+                               window_tables=d_tables, solve=spec.solve, continuum=spec.continuum,
+                               wash=wash_block(spec))
+            if spec.solve is not None:
+                compute_wash.solve_last = res[1]
+        if spec.solve is not None:
+            compute_wash.solve = _solve.normalize(spec.solve)
+            compute_wash.solve_last = compute_wash.solve_local = None
+        return compute_wash
     if spec.solve is not None:
         # the inverse sweep: always from the shared z-sum tables (Engine.sweep(solve=)); the records at
         # the solutions go to `out`, the results ride back on the function (run_local collects them)
@@ -1118,6 +1204,10 @@ def main(argv=None):
     ap.add_argument("--continuum", action="store_true",
                     help="the A/V z-sum as a converged z-integral on the continuum z rule of z_max in place of the "
                          "(nz, z_max) grid (a spec file's \"z_rule\": \"continuum\"); always through shared z-sum tables")
+    ap.add_argument("--wash-quadrature", action="store_true",
+                    help="Gamma_wash_over_H / deplete_DM_from_source points (sigma_v = 0 everywhere) on the y-grid "
+                         "quadrature in place of the ODE fallback (a spec file's \"wash_rule\": \"quadrature\"): "
+                         "window, --solve (Gamma_wash_over_H:LO:HI too), --reuse-zsums and --continuum then apply")
     ap.add_argument("--ode-max-steps", type=int, default=None,
                     help=f"cap on one ODE point's Radau steps (default {ODE_MAX_STEPS}; 0 = no cap)")
     ap.add_argument("--dist-backend", default="nccl",
@@ -1153,13 +1243,16 @@ def main(argv=None):
     if args.nz is not None or args.z_max is not None:
         spec.nz, spec.z_max = _native.zgrid(spec.nz if args.nz is None else args.nz,
                                             spec.z_max if args.z_max is None else args.z_max)
+    if args.wash_quadrature:
+        spec.wash_rule = "quadrature"
     if args.continuum:
         spec.z_rule = "continuum"
+    if args.solve is not None:
+        spec.solve = _solve.parse_cli(args.solve)
+    check_wash_spec(spec)
     check_z_rule(spec)
     if args.ode_max_steps is not None:
         spec.ode_max_steps = None if args.ode_max_steps == 0 else args.ode_max_steps
-    if args.solve is not None:
-        spec.solve = _solve.parse_cli(args.solve)
     if spec.solve is not None:
         check_solve_spec(spec)
     fitspec = fit_maps = None

@@ -115,7 +115,11 @@ enum lzq_field {
    * entry points; every other one refuses them as unknown fields */
   LZQ_F_WIN_Y0 = 64, LZQ_F_WIN_HALF_WIDTH = 65, LZQ_F_WIN_SIGMA_LO = 66, LZQ_F_WIN_SIGMA_HI = 67,
   LZQ_F_WIN_SIGMA = 68 /* sigma_lo and sigma_hi */, LZQ_F_WIN_SCALE = 69,
-  LZQ_F_WIN_TABLE = 70 /* table, from a double holding an integer */
+  LZQ_F_WIN_TABLE = 70 /* table, from a double holding an integer */,
+  /* fields of the point's lzq_ode_params block, accepted only by the *_wash grid entry points ("wash-out
+   * and source depletion" below); every other one refuses them as unknown fields */
+  LZQ_F_GAMMA_WASH = 96 /* Gamma_wash_over_H */,
+  LZQ_F_DEPLETE = 97 /* deplete_DM_from_source: value != 0 */
 };
 
 #define LZQ_MAX_AXES 8
@@ -562,6 +566,69 @@ typedef struct lzq_ode_params {
   int32_t deplete_DM_from_source;  /* fpy:282 */
   int32_t reserved;                /* 0 */
 } lzq_ode_params;                  /* 24 bytes */
+
+/* ---- wash-out and source depletion on the y-grid quadrature (PAPER §10 step 5) ---- */
+/* With sigma_v = 0 the system of fpy:270-286 is linear: Y_B has the integrating factor
+ * (x/x_1)^Gamma = (T_lo/T)^Gamma and the depletion term is the unwashed source, so on the fast path's
+ * own y-grid, with g its integrand (fpy:264-265) and w its trapezoid weights,
+ *
+ *   Y_B   = sum_j w_j g_j omega(T_j),     omega(T) = exp(-Gamma log(T / T_lo))
+ *   Y_chi = Y_chi0 - [deplete] sum_j w_j g_j          (one IEEE subtraction; nothing is clamped)
+ *
+ * Gamma = max(Gamma_wash_over_H, 0) (fpy:284), deplete = (deplete_DM_from_source != 0), T_lo =
+ * max(T_min_over_Tp T_p, 1e-30) (fpy:369, 389), Y_chi0 the fast path's Y_chi (fpy:376-384 = 389-399);
+ * the epilogue (fpy:413-417) then runs on (Y_B, Y_chi).  csrc/lzq_wash.h holds the one definition that
+ * the host and the device build.  Gamma = 0 takes neither the logarithm nor the exponential: omega is
+ * exactly 1, and with deplete = 0 every entry point below returns its namesake's bits.  The entry
+ * points read the z-sum tables of the shared-table mode, linspace or continuum (nz = LZQ_WASH_NZ_CONT
+ * names the continuum rule; the header is checked as the reuse kernels check it), and combine with a
+ * window block (base_win / d_win NULL: the point's Gaussian).  An opt-in mode: no default changes, and
+ * the ODE entry points below are untouched.
+ * Refused: sigma_v_chi_GeV_m2 > 0 after its max(., 0) (LZQ_EUNSUPPORTED) or a NaN in sigma_v or
+ * Gamma (LZQ_EINVAL), with a message naming the field, from the host-side checks; NaN yields from a
+ * kernel that meets such a block in device memory.  A regime that is neither thermal nor nonthermal
+ * starts thermal in the reference's ODE branch (fpy:399-400) but has no Y_chi on its fast path: here it
+ * is the fast path's rule (LZQ_EUNSUPPORTED from the grid entry points, NaN yields from explicit
+ * records), so such a point differs from what lzq_ode_* return for it.  Not built: sigma_v != 0, a momentum kernel F(k)
+ * together with wash-out, the dense (unshared) form, fractional depletion. */
+#define LZQ_WASH_NZ_CONT (-1)
+int lzq_wash_check_host(const lzq_ode_params* ode, int64_t n);
+/* The host build of omega: out[i] = omega(T(y[i])) with T(y) = T_p / sqrt(max(1 + 2y / max(beta_over_H,
+ * 1e-30), 1e-12)) (fpy:252-254) and libm's log and exp.  lzq_wash_check_host runs first.  No GPU. */
+int lzq_wash_factor_host(const lzq_point* pt, const lzq_ode_params* ode, const double* y, int64_t n, double* out);
+/* The device build: T(y) by the quadrature kernels' operations, their exponential (<= 1 ulp). */
+int lzq_wash_factor_batch(const lzq_point* pt, const lzq_ode_params* ode, const double* d_y, int64_t n, double* d_out,
+                          void* stream);
+/* lzq_yields_batch_reuse_window (d_win NULL: lzq_yields_batch_reuse) with point i's block d_ode[i]. */
+int lzq_yields_batch_reuse_wash(const lzq_point* d_points, int64_t n, int32_t n_y, int32_t nz, double z_max,
+                                const double* d_P, const int64_t* d_rep, const int32_t* d_table_index,
+                                int64_t n_tables, double* d_work, int64_t work_doubles, const lzq_window* d_win,
+                                const lzq_window_tables* d_tables, const lzq_ode_params* d_ode, lzq_yield* d_out,
+                                void* stream);
+/* lzq_sweep_grid_from_ztables[_window|_cont] with point i's block = *base_ode (a host struct) with the
+ * values of the grid's wash axes (LZQ_F_GAMMA_WASH, LZQ_F_DEPLETE) written into it, decoded from the
+ * flat index in the kernel beside the point and window fields.  Neither field contributes a z-sum
+ * table: d_work is what lzq_sweep_grid_ztables[_window|_cont] builds for the axis list WITHOUT them
+ * (the strides of the table fields do not depend on the axes between them).  Two axes writing one wash
+ * field are LZQ_EINVAL.  The records are those of lzq_yields_batch_reuse_wash on the decoded points
+ * and blocks, bit for bit. */
+int lzq_sweep_grid_from_ztables_wash(const lzq_point* base, const lzq_window* base_win, const lzq_ode_params* base_ode,
+                                     const lzq_axis* axes, int32_t n_axes, int64_t start, int64_t count, int32_t n_y,
+                                     int32_t nz, double z_max, const double* d_P, const double* d_work,
+                                     int64_t work_doubles, const lzq_window_tables* d_tables, lzq_yield* d_out,
+                                     void* stream);
+/* lzq_sweep_grid_solve: the same contract and stepping rule (csrc/lzq_solve.h), each evaluation one
+ * point of lzq_sweep_grid_from_ztables_wash.  LZQ_F_GAMMA_WASH is an allowed solve field next to every
+ * field allowed today (the DM_over_B = 5.357 question of PAPER §10 step 5).  New refusals
+ * (lzq_solve_check_host_wash; base_ode NULL there: lzq_solve_check_host, unchanged): Gamma solved and
+ * also an axis; lo < 0 for Gamma; LZQ_F_DEPLETE as the solve field; sigma_v != 0 or a NaN in the base block. */
+int lzq_sweep_grid_solve_wash(const lzq_point* base, const lzq_window* base_win, const lzq_ode_params* base_ode,
+                              const lzq_axis* axes, int32_t n_axes, const lzq_solve* solve, int64_t start,
+                              int64_t count, int32_t n_y, int32_t nz, double z_max, const double* d_P,
+                              const double* d_work, int64_t work_doubles, const lzq_window_tables* d_tables,
+                              lzq_yield* d_out, lzq_solve_result* d_sol, void* stream);
+int lzq_solve_check_host_wash(const lzq_solve* solve, const lzq_window* base_win, const lzq_ode_params* base_ode,
+                              const lzq_axis* axes, int32_t n_axes);
 
 #define LZQ_ODE_NT 800             /* fpy:207 build_tables(n=800), the n main() uses (fpy:387) */
 #define LZQ_ODE_WS_PER_POINT 3200  /* workspace doubles per point (spline coefficients): 4 x LZQ_ODE_NT */
