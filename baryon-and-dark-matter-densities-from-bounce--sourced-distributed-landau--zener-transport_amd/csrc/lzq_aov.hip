@@ -54,7 +54,7 @@ __global__ __launch_bounds__(kBlock, LZQ_MIN_WAVES) void yields_points_aov_kerne
     aov_override(s, aov[idx]);                                            // self.aov: fpy:261
     park(slots[w], s, epilogue_pre(pt, P), lane);
   }
-  point_yields<YB, EXPV, NZ>(slots, w, zt, nzp, tab, lane, truncate, out + idx);
+  point_yields<YB, EXPV, NZ, kClampArgFits<NZ>>(slots, w, zt, nzp, tab, lane, truncate, out + idx);
 }
 
 // lzq_ode_tables with d_aov: build_tables (fpy:207-212) with y(T) from the point (cfg) and A/V

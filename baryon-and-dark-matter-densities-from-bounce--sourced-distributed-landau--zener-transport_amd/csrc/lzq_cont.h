@@ -154,6 +154,9 @@ static inline const char* cont_build(double z_max, ContTable& t) {
   if (!(t.g4[0] > 0.0) || !((double)kTabN * 1077.0 * t.g4[n - 1] / t.g4[0] < 0x1p200))
     return "z_max: gamma4 of the first node breaks the inner loop's reduction";
   if (!(ldexp(t.omega[0], -kOmegaBias) >= 0x1p-1022)) return "z_max: the first node's weight underflows";
+  // a clamped node's term omega'_k v_c rounds away at every node (LZQ_CLAMP_ARG, lzq_exp2.h)
+  if (!clamp_arg_grid_ok([&](int k) { return ldexp(t.omega[k], -kOmegaBias); }, (int)n))
+    return "z_max: a weight is too large for a clamped node's term to round away";
   return nullptr;
 }
 

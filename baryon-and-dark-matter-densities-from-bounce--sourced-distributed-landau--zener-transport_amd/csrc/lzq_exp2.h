@@ -322,6 +322,74 @@ LZQ_HD double seg_node_dead(double Av, double Ts) { return Ts * fma_vvs(Av, Av, 
 LZQ_HD bool seg_clamped_or_dead(bool dead, double c2N, double g, double Mv) { return dead || seg_clamped(c2N, g, Mv); }
 LZQ_HD double seg_entry_lane(const double* tabp, bool dead) { return seg_entry(tabp, dead ? kTabMagic : kTabTClamp); }
 
+// The clamped argument (LZQ_CLAMP_ARG, lzq_quad.h).  The max above clamps the magic sum, that is the table
+// index; exp2_tab_scaled's s still comes from the unclamped t, so an underflowed node's stand-in value is
+// T''(KMIN) * ((r_k + A)^2 + beta) with a fractional part r_k that moves at every node and does no work: the
+// node's term omega' * v ~ omega * 2^-1506 is discarded by the accumulate's rounding whatever r_k is.  With
+// the argument itself clamped, a node with t <= M + KMIN is evaluated AT u = KMIN: r = 0, s = A, and its
+// value is the one number
+//   v_c = T''(KMIN) * fma(A, A, beta) = seg_node_dead(A, seg_entry(tab, M + KMIN))
+// (clamp_arg_s: a select on the comparison the max already makes; exp2_tab_scaled_clamp_arg: the general
+// clamped node with it; a node above the clamp keeps exp2_tab_scaled's bits).  t only falls with k, so from
+// the first node at which every live lane is clamped the node value is fixed by the pass test and the rest
+// of the pass is F's accumulate alone (zsum_dispatch's clamped branch).  A dead lane (c2N = +0.0, t = M)
+// is never clamped and keeps its s = fma(+0 * g, A) = A: seg_node_dead on T''[0], as before.
+//
+// F's bits do not move: either stand-in's term is below half the smallest subnormal, omega'_k v_c < 2^-1075,
+// so fma(omega'_k, v, F) returns F whether F is +0, subnormal or normal.  That bound is a condition on the
+// grid's weights; clamp_arg_rounds_away states it and every producer of a grid checks it on the host.
+//
+// The select is a compare and two v_cndmask_b32 on the halves of s, in place: three VALU per node.  A's low
+// word is 0, an inline constant; its high word a_hi is handed over by the caller, which on the device holds it
+// in a VGPR filled once per loop (clamp_arg_hi: opaque, so that the compiler neither hoists it out of the
+// y-loop, where it is one register more than the kernel has, nor re-forms it per node).
+constexpr uint32_t kSqAHi = (uint32_t)(__builtin_bit_cast(uint64_t, kSqA) >> 32);
+static_assert((uint32_t)__builtin_bit_cast(uint64_t, kSqA) == 0u, "A's low word is 0");
+LZQ_HD uint32_t clamp_arg_hi() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint32_t a;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(a) : "i"(kSqAHi));
+  return a;
+#else
+  return kSqAHi;
+#endif
+}
+LZQ_HD double clamp_arg_s(double t, double s, uint32_t a_hi = kSqAHi) {
+  const bool clamped = t <= kTabTClamp;
+  lzq_u32x2 w = __builtin_bit_cast(lzq_u32x2, s);
+  w[0] = clamped ? 0u : w[0];
+  w[1] = clamped ? a_hi : w[1];
+  return __builtin_bit_cast(double, w);
+}
+LZQ_HD double exp2_tab_scaled_clamp_arg(double c2N, double g, const double* tabp) {
+  const double t = __builtin_fma(c2N, g, kTabMagic);
+  const double tc = __builtin_fmax(t, kTabTClamp);
+  const uint32_t k = (uint32_t)__builtin_bit_cast(uint64_t, tc);
+  const double Ts = tab_scale(tabp[tab_byte_addr(k) >> 3], k);
+  const double s = clamp_arg_s(t, __builtin_fma(c2N, g, (kTabMagic + kSqA) - t));
+  return Ts * __builtin_fma(s, s, kSqBeta);
+}
+// v_c on the host, from the one entry it reads (KMIN is a whole number of octaves: entry 0)
+static_assert(kTabKMin % kTabN == 0, "the clamp constant reads entry 0");
+static inline double clamp_arg_value() {
+  const double T0 = __builtin_bit_cast(double, tab_entry_bits(tab_exact(0), 0));
+  return seg_node_dead(kSqA, seg_entry(&T0, kTabTClamp));
+}
+// whether omega' * v_c < 2^-1075 for a scaled weight omega' = omega * 2^-512 >= 0, decided on the binary
+// exponents (omega' < 2^(a+1) and v_c < 2^(b+1), so the product is below 2^(a+b+2)): no product is formed
+static inline bool clamp_arg_rounds_away(double omega_scaled, double v_c) {
+  if (!(omega_scaled > 0.0)) return omega_scaled == 0.0;
+  if (!(omega_scaled <= 0x1.fffffffffffffp1023) || !(v_c > 0.0)) return false;
+  return ilogb(omega_scaled) + ilogb(v_c) + 2 <= -1075;
+}
+template <class Omega>
+static inline bool clamp_arg_grid_ok(Omega omega_scaled, int n) {
+  const double v_c = clamp_arg_value();
+  for (int k = 0; k < n; ++k)
+    if (!clamp_arg_rounds_away(omega_scaled(k), v_c)) return false;
+  return true;
+}
+
 // Frozen stretches.  gamma4 saturates, so g4_k moves ever less with k, and a lane's rounded
 // intermediate -- s = fma(c2N, g, A) on a zero pass, t = fma(c2N, g, M) on a clamp-free one -- stops
 // changing long before the pass ends (on small |c2N| it never changes).  Both are correctly rounded

@@ -66,7 +66,7 @@ __global__ __launch_bounds__(kBlock, LZQ_MIN_WAVES) void yields_points_kernel(co
     const double thi = T_hi ? T_hi[idx] : pt.T_max_over_Tp * pt.T_p_GeV;  // fpy:368
     park(slots[w], quad_setup(pt, P, tlo, thi, n_y), epilogue_pre(pt, P), lane);
   }
-  point_yields<YB, EXPV, NZ>(slots, w, zt, nzp, tab, lane, truncate, out + idx);
+  point_yields<YB, EXPV, NZ, kClampArgFits<NZ>>(slots, w, zt, nzp, tab, lane, truncate, out + idx);
 }
 
 template <int YB, int EXPV, int NZ>
@@ -387,6 +387,11 @@ int build_ztable(int32_t nz, double z_max, HostZGrid& h) {
       return fail(LZQ_EINVAL, "z grid (nz = %d, z_max = %g): gamma4[1] = %g breaks the inner loop's reduction", nz,
                   z_max, g1);
   }
+  // a clamped node stands for an underflowed term with the clamped argument's value v_c (LZQ_CLAMP_ARG,
+  // lzq_exp2.h): its term omega'_k v_c has to stay below half the smallest subnormal at every node
+  if (!lzq::clamp_arg_grid_ok([&](int k) { return ldexp(h.omega[k], -lzq::kOmegaBias); }, nz))
+    return fail(LZQ_EINVAL, "z grid (nz = %d, z_max = %g): a weight is too large for a clamped node's term to round "
+                "away", nz, z_max);
   return LZQ_OK;
 }
 

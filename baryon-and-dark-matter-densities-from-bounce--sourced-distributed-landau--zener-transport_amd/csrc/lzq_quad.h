@@ -21,7 +21,7 @@
 
 namespace lzq {
 
-// The six fast-path levels of the dense z-sum and y-loop.  Each is a switch only because a host test
+// The seven fast-path levels of the dense z-sum and y-loop.  Each is a switch only because a host test
 // builds it with =0 and pins the result to the recorded machine code of the commit before it; the full
 // account of every level is DESIGN.md §4.1.  A level whose "needs" are not at their defaults is off.
 //
@@ -41,6 +41,10 @@ namespace lzq {
 //   LZQ_ACC_FEED      0, 1     the accumulate-only loops (zsum_dead, zsum_held, single    all five at their
 //                              and grouped) read omega' from the image's packed array:    defaults
 //                              one 64-byte line per 8-node batch, not two
+//   LZQ_CLAMP_ARG     0, 1     a clamped node is evaluated at the clamped argument        all six at their
+//                              u = KMIN (s = A), so its value is one number, and a        defaults
+//                              clamped pass runs as F's accumulate alone from the batch
+//                              at which its last live lane clamps
 #ifndef LZQ_ZERO_SEG
 #define LZQ_ZERO_SEG 1
 #endif
@@ -59,14 +63,23 @@ namespace lzq {
 #ifndef LZQ_ACC_FEED
 #define LZQ_ACC_FEED 1
 #endif
+#ifndef LZQ_CLAMP_ARG
+#define LZQ_CLAMP_ARG 1
+#endif
 static_assert(LZQ_GROUP_SEG == 0 || LZQ_GROUP_SEG == 2 || LZQ_GROUP_SEG == 4, "LZQ_GROUP_SEG is 0, 2 or 4");
 static_assert(LZQ_PASS_LEAN == 0 || LZQ_PASS_LEAN == 1, "LZQ_PASS_LEAN is 0 or 1");
 static_assert(LZQ_ACC_FEED == 0 || LZQ_ACC_FEED == 1, "LZQ_ACC_FEED is 0 or 1");
+static_assert(LZQ_CLAMP_ARG == 0 || LZQ_CLAMP_ARG == 1, "LZQ_CLAMP_ARG is 0 or 1");
 constexpr int kFrozenSeg = (LZQ_ZERO_SEG != 0 && LZQ_DEAD_SEG != 0) ? LZQ_FROZEN_SEG : 0;
 constexpr int kGroupSeg = kFrozenSeg >= 1 ? LZQ_GROUP_SEG : 0;
 constexpr bool kLean = LZQ_ZERO_SEG == 1 && LZQ_DEAD_SEG == 1 && LZQ_FROZEN_SEG == 2 && LZQ_GROUP_SEG == 4 &&
                        LZQ_PASS_LEAN == 1;
 constexpr bool kAccFeed = kLean && LZQ_ACC_FEED == 1;
+constexpr bool kClampArg = kAccFeed && LZQ_CLAMP_ARG == 1;
+// the per-point dense kernels: on wherever the kernel keeps its 64 VGPRs without scratch with it
+// (tools/kernel_resources.py; tests/test_zsum_clamp_arg_host.py)
+template <int NZ>
+constexpr bool kClampArgFits = kClampArg && NZ == 0;
 
 constexpr int kNZ = LZQ_NZ;
 constexpr int kWaveSize = 64;
@@ -428,7 +441,7 @@ __device__ __forceinline__ double c2_scale() { return EXPV == kExpTable ? (doubl
 // (LZQ_GROUP_SEG, yb_group below; tests/test_zsum_group_host.py, tests/test_gpu_zsum_group.py), and all of
 // them, grouped or not, read omega' from the packed array of the grid's image, one line per 8-node batch
 // instead of two (LZQ_ACC_FEED, acc_omega; tests/test_zsum_feed_host.py, tests/test_gpu_zsum_feed.py).
-template <int YB, int EXPV, bool CLAMP = true>
+template <int YB, int EXPV, bool CLAMP = true, bool CARG = kClampArg>
 __device__ __forceinline__ void zsum(const ZNode* __restrict__ zt, const double* tab, const double (&c2)[YB],
                                      double (&F)[YB], int kend) {
 #pragma unroll
@@ -444,6 +457,9 @@ __device__ __forceinline__ void zsum(const ZNode* __restrict__ zt, const double*
     for (int i = 0; i < kPolyDeg; ++i) Bv[i] = TabPoly<kTabBits, kPolyDeg>::B[i];
     if constexpr (!kSqForm) Bv[0] = vgpr_const(Bv[0]);
     const char* tabb = reinterpret_cast<const char*>(tab);
+    // (LZQ_CLAMP_ARG: A's high word for the clamped lanes' select, in a VGPR for this loop alone)
+    [[maybe_unused]] uint32_t Ah = 0;
+    if constexpr (CLAMP && CARG && kSqForm) Ah = clamp_arg_hi();
     for (int k = 0; k < kend; k += kKUnroll) {
       double g4[kKUnroll], om[kKUnroll];
 #pragma unroll
@@ -452,40 +468,48 @@ __device__ __forceinline__ void zsum(const ZNode* __restrict__ zt, const double*
         om[kk] = zt[k + kk].omega;
       }
       // phases: reduction + addresses for the whole batch, then the lookups (in flight
-      // together), then polynomial + accumulate
-      double r[YB][kKUnroll], T[YB][kKUnroll];
-      uint32_t kc[YB][kKUnroll], a[YB][kKUnroll];
+      // together), then polynomial + accumulate.  (LZQ_CLAMP_ARG: the clamped loop runs the phases on the two
+      // halves of the batch in turn -- with the select's masks and A's high word beside it, eight nodes in
+      // flight are a register more than the kernel has)
+      constexpr int kPh = (CLAMP && CARG && kSqForm && kKUnroll % 2 == 0) ? kKUnroll / 2 : kKUnroll;
 #pragma unroll
-      for (int kk = 0; kk < kKUnroll; ++kk)
+      for (int h = 0; h < kKUnroll; h += kPh) {
+        double r[YB][kPh], T[YB][kPh];
+        uint32_t kc[YB][kPh], a[YB][kPh];
 #pragma unroll
-        for (int b = 0; b < YB; ++b) {
-          const double t = __builtin_fma(c2[b], g4[kk], Mv);
-          if constexpr (kSqForm) {
-            r[b][kk] = __builtin_fma(c2[b], g4[kk], MAv - t);  // s = r + A (lzq_exp2.h)
-          } else {
-            const double kd = t - Mv;
-            r[b][kk] = __builtin_fma(c2[b], g4[kk], -kd);
+        for (int kk = 0; kk < kPh; ++kk)
+#pragma unroll
+          for (int b = 0; b < YB; ++b) {
+            const double t = __builtin_fma(c2[b], g4[h + kk], Mv);
+            if constexpr (kSqForm) {
+              r[b][kk] = __builtin_fma(c2[b], g4[h + kk], MAv - t);  // s = r + A (lzq_exp2.h)
+              // (LZQ_CLAMP_ARG: a clamped lane takes the clamped argument's s = A, on the max's own comparison)
+              if constexpr (CLAMP && CARG) r[b][kk] = clamp_arg_s(t, r[b][kk], Ah);
+            } else {
+              const double kd = t - Mv;
+              r[b][kk] = __builtin_fma(c2[b], g4[h + kk], -kd);
+            }
+            const double tc = CLAMP ? __builtin_fmax(t, kTClamp) : t;
+            kc[b][kk] = (uint32_t)__builtin_bit_cast(uint64_t, tc);
+            a[b][kk] = tab_byte_addr(kc[b][kk]);
           }
-          const double tc = CLAMP ? __builtin_fmax(t, kTClamp) : t;
-          kc[b][kk] = (uint32_t)__builtin_bit_cast(uint64_t, tc);
-          a[b][kk] = tab_byte_addr(kc[b][kk]);
-        }
 #pragma unroll
-      for (int kk = 0; kk < kKUnroll; ++kk)
+        for (int kk = 0; kk < kPh; ++kk)
 #pragma unroll
-        for (int b = 0; b < YB; ++b) T[b][kk] = *reinterpret_cast<const double*>(tabb + a[b][kk]);
+          for (int b = 0; b < YB; ++b) T[b][kk] = *reinterpret_cast<const double*>(tabb + a[b][kk]);
 #pragma unroll
-      for (int kk = 0; kk < kKUnroll; ++kk)
+        for (int kk = 0; kk < kPh; ++kk)
 #pragma unroll
-        for (int b = 0; b < YB; ++b) {
-          const double Ts = tab_scale(T[b][kk], kc[b][kk]);
-          if constexpr (kSqForm) {
-            F[b] = __builtin_fma(om[kk], Ts * __builtin_fma(r[b][kk], r[b][kk], kSqBeta), F[b]);
-          } else {
-            const double q = tab_q_with<kPolyDeg>(r[b][kk], Bv);
-            F[b] = __builtin_fma(om[kk], __builtin_fma(Ts, q, Ts), F[b]);
+          for (int b = 0; b < YB; ++b) {
+            const double Ts = tab_scale(T[b][kk], kc[b][kk]);
+            if constexpr (kSqForm) {
+              F[b] = __builtin_fma(om[h + kk], Ts * __builtin_fma(r[b][kk], r[b][kk], kSqBeta), F[b]);
+            } else {
+              const double q = tab_q_with<kPolyDeg>(r[b][kk], Bv);
+              F[b] = __builtin_fma(om[h + kk], __builtin_fma(Ts, q, Ts), F[b]);
+            }
           }
-        }
+      }
     }
   } else {
     for (int k = 0; k < kend; k += kKUnroll) {
@@ -573,18 +597,23 @@ __device__ __forceinline__ void zsum_uniform_lane(const ZNode* __restrict__ zt, 
 // order from F = 0.  No node is skipped.  v0 takes the loop's one pinned VGPR pair; omega' is the
 // instruction's scalar operand, and g4 is not read.  FEED (LZQ_ACC_FEED): omega' comes from the packed
 // array behind the grid's nzp nodes (acc_omega), the same bits out of one 64-byte line per batch.
+// kbeg > 0 (LZQ_CLAMP_ARG): the clamped suffix of a pass without dead lanes, nodes kbeg .. kend with Ts the
+// entry of M + KMIN, so that v0 is the clamped argument's value v_c; F carries on from the prefix.
 template <int YB, bool FEED = false>
-__device__ __forceinline__ void zsum_dead(const ZNode* __restrict__ zt, int nzp, double Ts, double (&F)[YB], int kend) {
+__device__ __forceinline__ void zsum_dead(const ZNode* __restrict__ zt, int nzp, double Ts, double (&F)[YB], int kend,
+                                          int kbeg = 0) {
+  if (kbeg == 0) {
 #pragma unroll
-  for (int b = 0; b < YB; ++b) F[b] = 0.0;
-  // (YB > 1: the chains start from the same 0 and add the same terms; opaque starts keep them YB
-  // chains of YB fma per node -- dense work -- instead of one chain the compiler copies)
-  if constexpr (YB > 1) {
+    for (int b = 0; b < YB; ++b) F[b] = 0.0;
+    // (YB > 1: the chains start from the same 0 and add the same terms; opaque starts keep them YB
+    // chains of YB fma per node -- dense work -- instead of one chain the compiler copies)
+    if constexpr (YB > 1) {
 #pragma unroll
-    for (int b = 0; b < YB; ++b) asm volatile("" : "+v"(F[b]));
+      for (int b = 0; b < YB; ++b) asm volatile("" : "+v"(F[b]));
+    }
   }
   const double v0 = seg_node_dead(vgpr_const(kSqA), Ts);
-  for (int k = 0; k < kend; k += kKUnroll) {
+  for (int k = kbeg; k < kend; k += kKUnroll) {
     double om[kKUnroll];
 #pragma unroll
     for (int kk = 0; kk < kKUnroll; ++kk) om[kk] = acc_omega<FEED>(zt, nzp, k + kk);
@@ -698,6 +727,11 @@ __device__ __forceinline__ double shfl_xor_rederived(double v, int off) {
 // FEEDOK (LZQ_ACC_FEED): the accumulate-only loops of an untruncated pass may read the packed omega' array;
 // false for the table mode, which like the truncated pass stays on the nodes (the dense kernels' controls).
 //
+// CARG (LZQ_CLAMP_ARG, per kernel): the clamped argument.  A template parameter beside the switch because the
+// per-point kernels on the default grid (yields_points_kernel and yields_points_aov_kernel with NZ = 1200) do
+// not fit 64 VGPRs with it -- 12 bytes of scratch, outside the z-loops -- and run without (kClampArgFits);
+// F's bits are the same either way.
+//
 // after_general (LZQ_PASS_LEAN; yb_wave's): called at the end of the branches that ran the table-lookup
 // loop zsum<>, and of no other.  What the caller keeps in registers across the lean loops it re-forms
 // there, so that on the control-flow graph those values are dead through zsum<>, which has no room for
@@ -706,7 +740,7 @@ struct NoAfterGeneral {
   __device__ __forceinline__ void operator()() const {}
 };
 
-template <int YB, int EXPV, int NZ = 0, bool FEEDOK = true, typename After = NoAfterGeneral>
+template <int YB, int EXPV, int NZ = 0, bool FEEDOK = true, bool CARG = kClampArg, typename After = NoAfterGeneral>
 __device__ __forceinline__ bool zsum_dispatch(const ZNode* __restrict__ zt, int nzp, const double* tab,
                                               const double (&c2)[YB], double (&F)[YB], int truncate = 0,
                                               const After& after_general = After()) {
@@ -847,8 +881,25 @@ __device__ __forceinline__ bool zsum_dispatch(const ZNode* __restrict__ zt, int 
               return __all(c) != 0;
             },
             [&](int k) { return zt[k].g4; }, kend, kKUnroll);
-        if (k2 > 0) zsum<YB, EXPV, true>(zt, tab, c2e, F, k2);
-        if (mixed) {
+        if (k2 > 0) zsum<YB, EXPV, true, CARG>(zt, tab, c2e, F, k2);
+        if constexpr (CARG) {
+          // The clamped argument (LZQ_CLAMP_ARG): from k2 on every live lane's node is evaluated at u = KMIN
+          // (s = A) and a dead lane's s is A already, so each lane's node value is one number -- the entry
+          // times fma(A, A, beta) -- and the suffix is F's accumulate alone, in node order, carrying F from
+          // the prefix: zsum_dead's loop from k2 with v_c, or zsum_held with the value of each lane's own entry
+          if (mixed) {
+            const double Av = vgpr_const(kSqA);
+            double v[YB];
+#pragma unroll
+            for (int b = 0; b < YB; ++b) v[b] = seg_node_dead(Av, seg_entry_lane(tab, dead[b]));
+            if (kAccFeed && FEEDOK && !truncate) zsum_held<YB, kAccFeed && FEEDOK>(zt, nz, v, F, kend, k2);
+            else zsum_held<YB>(zt, nz, v, F, kend, k2);
+          } else {
+            const double Tc = uniform(seg_entry(tab, kTabTClamp));
+            if (kAccFeed && FEEDOK && !truncate) zsum_dead<YB, kAccFeed && FEEDOK>(zt, nz, Tc, F, kend, k2);
+            else zsum_dead<YB>(zt, nz, Tc, F, kend, k2);
+          }
+        } else if (mixed) {
           double Tl[YB];
 #pragma unroll
           for (int b = 0; b < YB; ++b) Tl[b] = seg_entry_lane(tab, dead[b]);
@@ -1031,7 +1082,8 @@ __device__ __forceinline__ int yb_group(Slot* slots, int w, const ZNode* __restr
 // operations in the same lane order in every mode, so Y_B is bit-identical.
 enum YbMode { kYbDense = 0, kYbReuse = 1, kYbTable = 2 };
 
-template <int YB, int EXPV, int MODE = kYbDense, int NZ = 0, typename Win = SlotGaussWindow, typename Slot>
+template <int YB, int EXPV, int MODE = kYbDense, int NZ = 0, typename Win = SlotGaussWindow, bool CARG = kClampArg,
+          typename Slot>
 __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int nzp, const double* tab, int truncate,
                           const double* __restrict__ Fin = nullptr, double* __restrict__ Fout = nullptr) {
   if (slots[w].s.empty) return 0.0;
@@ -1094,7 +1146,7 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
       if constexpr (kLeanHere) {
         // y, e^y and the weight stay live through the lean loops; a pass that ran the table-lookup loop
         // re-forms them on its own branch (zsum_dispatch's after_general), as every pass did before
-        grp = zsum_dispatch<YB, EXPV, NZ, MODE == kYbDense>(zt, nzp, tab, c2, F, truncate, [&]() {
+        grp = zsum_dispatch<YB, EXPV, NZ, MODE == kYbDense, CARG>(zt, nzp, tab, c2, F, truncate, [&]() {
           int wa = w;
           asm volatile("" : "+s"(wa));
           const int la = lane_id();
@@ -1103,7 +1155,7 @@ __device__ double yb_wave(Slot* slots, int w, const ZNode* __restrict__ zt, int 
             y_triple<true>(slots[wa].s, base + b * kWaveSize + la, n, interior, yv[b], ey[b], wt[b]);
         });
       } else {
-        grp = zsum_dispatch<YB, EXPV, NZ, MODE == kYbDense>(zt, nzp, tab, c2, F, truncate);
+        grp = zsum_dispatch<YB, EXPV, NZ, MODE == kYbDense, CARG>(zt, nzp, tab, c2, F, truncate);
       }
       if constexpr (MODE == kYbTable) {
 #pragma unroll
@@ -1203,11 +1255,11 @@ __device__ __forceinline__ void park(WaveSlot& slot, const QuadSetup& s, const E
   __builtin_amdgcn_wave_barrier();
 }
 
-// Quadrature of the parked point, then lane 0 stores its yields.
-template <int YB, int EXPV, int NZ>
+// Quadrature of the parked point, then lane 0 stores its yields.  (CARG: LZQ_CLAMP_ARG for this kernel.)
+template <int YB, int EXPV, int NZ, bool CARG = kClampArg>
 __device__ __forceinline__ void point_yields(WaveSlot* slots, int w, const ZNode* __restrict__ zt, int nzp,
                                              const double* tab, int lane, int truncate, lzq_yield* out) {
-  const double Y_B = yb_wave<YB, EXPV, kYbDense, NZ>(slots, w, zt, nzp, tab, truncate);
+  const double Y_B = yb_wave<YB, EXPV, kYbDense, NZ, SlotGaussWindow, CARG>(slots, w, zt, nzp, tab, truncate);
   if (lane == 0) *out = epilogue_finish(slots[w].e, Y_B);
 }
 

@@ -44,7 +44,14 @@ point's scalar loads touch before and after -- an 8-node batch is two lines of t
 of the packed array; a group's sweep loads each batch once for all its chains.  No instruction count
 changes; what the array buys is feed time (profiles/round13).
 
-    python tools/uniform_segment_share.py
+Last, the clamped argument (LZQ_CLAMP_ARG), planned by tests/zsum_clamp_arg_host.cpp: the passes that take
+zsum_dispatch's clamped branch, their k2, the suffix nodes that run as F's accumulate alone instead of the
+six-operation node (t, w, s, q and v fewer: three FMA, one ADD and one MUL) and the prefix nodes of the clamped
+general loop, which gain the select (a compare and two v_cndmask_b32), with the VALU count and mix they predict
+from the PMC of the build without it (profiles/round15/parent_pmc_summary.json) and the time at four
+SIMD-cycles per VALU instruction.  `--write` records that section as profiles/round15/clamp_arg_plan.json.
+
+    python tools/uniform_segment_share.py [--write]
 """
 import json
 import os
@@ -59,6 +66,7 @@ import test_zsum_frozen_host as HF        # noqa: E402
 import test_zsum_group_host as HG         # noqa: E402
 import test_zsum_mixed_host as HM         # noqa: E402
 import test_zsum_feed_host as HFD         # noqa: E402
+import test_zsum_clamp_arg_host as HCA    # noqa: E402
 import zsum_ref as Z                      # noqa: E402
 
 
@@ -168,6 +176,45 @@ def feed_counts(g, c2_nodes):
         "lines_saved_share": fed_batches / before}}
 
 
+def clamp_arg_counts(g, c2):
+    """The clamped branch of LZQ_CLAMP_ARG on the passes of c2, and what it predicts from the parent's PMC."""
+    import ctypes
+    import subprocess
+    import tempfile
+    so = os.path.join(tempfile.mkdtemp(), "zsum_clamp_arg_host.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I",
+                    os.path.join(ROOT, HCA.PKG_NAME, "csrc"), os.path.join(ROOT, "tests", "zsum_clamp_arg_host.cpp"),
+                    "-o", so], check=True)
+    L = ctypes.CDLL(so)
+    L.zca_passes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, HCA.DP, HCA.DP, ctypes.c_int, HCA.DP,
+                             ctypes.c_long, HCA.DP, HCA.DP, HCA.UP, HCA.IP]
+    plan = HCA.run(L, g, c2, HCA.SEG)[3]
+    branch = (plan[:, 0] == HCA.SPLIT) | (plan[:, 0] == HCA.MIXED)
+    nodes = int(plan[:, 2].sum())
+    k2, kend = plan[branch, 1], plan[branch, 2]
+    suffix, prefix = int((kend - k2).sum()), int(k2.sum())
+    p15 = _parent("round15")
+    saved = (5.0 * suffix - 3.0 * prefix) / nodes
+    mix = dict(p15["valu_mix_per_wave_node"])
+    mix["fma_f64"] -= 3.0 * suffix / nodes       # t, s, q
+    mix["add_f64"] -= suffix / nodes             # w
+    mix["mul_f64"] -= suffix / nodes             # v
+    valu = p15["valu_insts_per_wave_node"] - saved
+    return {"clamp_arg": {
+        "passes_clamped_branch": np.flatnonzero(branch).tolist(), "k2": k2.tolist(),
+        "passes_with_suffix": int((k2 < kend).sum()), "passes_mixed": np.flatnonzero(plan[:, 0] == HCA.MIXED).tolist(),
+        "nodes_suffix_accumulate_only": suffix, "suffix_share": suffix / nodes,
+        "nodes_clamped_general_loop": prefix, "clamped_general_share": prefix / nodes,
+        "valu_saved_per_point": 5 * suffix, "valu_added_per_point": 3 * prefix,
+        "parent_valu_per_wave_node": p15["valu_insts_per_wave_node"],
+        "predicted_valu_per_wave_node": valu,
+        "predicted_valu_mix_per_wave_node": mix,
+        "predicted_flop_per_point": 64.0 * (2.0 * mix["fma_f64"] + mix["mul_f64"] + mix["add_f64"]) * nodes,
+        "parent_cycles_per_wave_node": p15["cycles_per_wave_node_per_simd"],
+        "predicted_cycles_saved_per_wave_node_at_4_per_valu": 4.0 * saved,
+        "predicted_time_ratio_at_4_cycles_per_valu": 1.0 - 4.0 * saved / p15["cycles_per_wave_node_per_simd"]}}
+
+
 def main():
     B, Tp, I_p = 100.0, 100.0, 0.34                  # yields_config_equal_mass.json (C2's base)
     y_of = lambda T: 0.5 * B * ((Tp / T) ** 2 - 1.0)
@@ -199,7 +246,12 @@ def main():
     mix9 = dict(p9["valu_mix_per_wave_node"])
     mix9["fma_f64"] -= 2.0 * dead / nodes
     mix9["mul_f64"] -= dead / nodes
-    print(json.dumps({**grouped, **frozen_counts(g, c2), **lean_counts(g, c2),
+    ca = clamp_arg_counts(g, c2)
+    if "--write" in sys.argv[1:]:
+        os.makedirs(os.path.join(ROOT, "profiles", "round15"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "round15", "clamp_arg_plan.json"), "w") as f:
+            json.dump(ca["clamp_arg"], f, indent=1)
+    print(json.dumps({**grouped, **frozen_counts(g, c2), **lean_counts(g, c2), **ca,
         "passes": int(len(path)), "nodes_per_point": nodes,
         "passes_whole_uniform": int(((path == H.ZERO) | (path == H.DEAD)).sum()),
         "passes_clamp_free": int((path == H.FREE).sum()),
